@@ -14,6 +14,11 @@ of each rank's own elapsed time).
 Rank 0 prints ONE JSON line, the headline, LAST (the contract's keys, roofline, cpu_baseline summary; under 8 KB),
 preceded, when extras ran, by one '#'-prefixed digest line of them; the full extras go to --extras-out. See
 DESIGN.md "Measurement" and section 10 for the roofline accounting and the output format.
+
+A plain run (no --full) does only what the headline figure needs: set-up, warm-up, the timed steps, the output dump
+when --dump-outputs is given, and the headline line (cpu_baseline null). --full adds everything else the benchmark
+measures: the CPU baseline (--cpu-baseline) and the extras (--extras: C3, the C4 variants, the z sweep, the HAL and
+software routes; C5 under torch.distributed.run).
 """
 from __future__ import annotations
 
@@ -60,6 +65,12 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=128, help="codeblocks per GPU per step (configs[1]: 128)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (--cpu-baseline) and the "
+                         "extras (--extras); without it both are left out, whatever those two options say")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (every codeblock's packed message "
+                         "bytes and result record) as DIR/<name>.npy in float32")
     ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
     ap.add_argument("--cpu-reps", type=int, default=10000,
                     help="timed single-CB decodes per CPU thread (R >= 200; the default is about 0.9 s per thread on "
@@ -457,6 +468,26 @@ def torch_device_index() -> int:
     return torch.cuda.current_device()
 
 
+DUMP_MAX_BYTES = 60_000_000          # under 64 MB with the .npy headers, whichever megabyte is meant
+
+
+def dump_outputs(out_dir: Path, rank: int, world: int, arrays) -> None:
+    """--dump-outputs: what the timed path's last step left for its caller (device tensors by name: every codeblock's
+    packed message bytes, one out_stride row per CB, and its 4-byte result record) as <name>.npy in float32, one
+    byte per element (<name>.rank<r>.npy under torch.distributed.run). The dump is at most DUMP_MAX_BYTES over all
+    ranks and arrays: an array over its share is cut to a fixed sample of its flattened elements (indices drawn
+    with seed 0, ascending), the same from run to run."""
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_MAX_BYTES // 4 // (world * len(arrays))       # float32 elements per array
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float32)
+        if a.size > share:
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(out_dir / (f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"), a)
+
+
 HEADLINE_MAX_BYTES = 8192
 EXTRAS_PREFIX = "# extras digest: "
 HEADLINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -656,6 +687,9 @@ def main():
     if world > 1:
         dist.barrier()
     kernel_ms = ev_start.elapsed_time(ev_end) / args.steps
+    if args.dump_outputs:
+        dump_outputs(Path(args.dump_outputs), rank, world,
+                     {"messages": d_out.view(n, out_stride), "results": d_res.view(n, 4)})
 
     from srsran_projectvtlmo_amd.multi_gpu import job_window, max_over_ranks
     if world > 1:
@@ -704,11 +738,14 @@ def main():
                      "source": "profiles/pmc_traffic.json (rocprofv3 --pmc SQ_ACTIVE_INST_VALU, SQ_INSTS_VALU) / live "
                                "kernel time"}
 
+    # everything below the headline's own figures runs under --full only
+    run_cpu = args.full and args.cpu_baseline == "auto"
+    run_extras = args.full and args.extras == "auto"
     extra, cpu_base = {}, None
-    if rank == 0 and world == 1 and args.cpu_baseline == "auto":
+    if rank == 0 and world == 1 and run_cpu:
         cpu_base = cpu_baseline(args.cpu_reps)
         extra["cpu_baseline_detail"] = cpu_base
-    if world == 1 and args.extras == "auto":
+    if world == 1 and run_extras:
         extra.update({"c3": extra_c3(ctx, stream), "c4": extra_c4(ctx, stream),
                       # SURVEY 8d's own C4 recipe, quantize(2.0 (1 - 2b) + N(0, 1), 8): the code-rate-0.87 TB of UE0
                       # fails at this SNR, so the slot runs more iterations and the goodput collapses
@@ -718,8 +755,8 @@ def main():
         blob = hal_slot_blob(ctx)
         extra["hal"] = extra_hal(ctx, stream, blob=blob)
         extra["sw_route"] = label_auto_route(extra_sw_route(ctx, stream, blob=blob,
-                                                            cpu_leg=args.cpu_baseline == "auto"))
-    if world > 1 and args.extras == "auto":
+                                                            cpu_leg=run_cpu))
+    if world > 1 and run_extras:
         # C5 (configs[4]): one 100 MHz cell per GPU (seeds 3..), every rank decodes its own C4 slot; no collective
         c5 = extra_c4(ctx, stream, seed=3 + rank)
         per = gather_objects([c5["us_per_slot"], c5["tb_crc_ok"]])

@@ -74,6 +74,36 @@ def test_extras_digest_of_round5_record_is_small():
     assert len(txt.encode()) + len(json.dumps(_headline()).encode()) < 12288
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d" and a.cpu_baseline == "auto" and a.extras == "auto"
+    # a plain run's line: the contract's keys with a null cpu_baseline
+    line = bench.headline_line(gbps=8.11, world=1, steps=20, warmup=5, elapsed=20 * 1.333e-4, kernel_ms=0.1327, n=128,
+                               total_cbs=128 * 20, traffic=None, prov=None, secondary=None, cpu_base=None)
+    assert all(k in line for k in bench.HEADLINE_KEYS) and line["cpu_baseline"] is None
+    assert abs(line["ms_per_step"] - 0.1333) < 1e-9
+
+
+def test_dump_outputs_writes_float32_arrays_within_the_size_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    msgs = torch.arange(6 * 32, dtype=torch.int64).remainder(251).to(torch.uint8).view(6, 32)
+    res = torch.tensor([[1, 3, 0, 0]] * 6, dtype=torch.uint8)
+    bench.dump_outputs(tmp_path / "a", 0, 1, {"messages": msgs, "results": res})
+    got = np.load(tmp_path / "a" / "messages.npy")
+    assert got.dtype == np.float32 and got.shape == (6, 32) and np.array_equal(got, msgs.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "results.npy"), res.numpy())
+    # over the limit: a fixed sample of the flattened array, the same from run to run, ranks named apart
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 2 * 2 * 40)
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, 1, 2, {"messages": msgs, "results": res})
+    b, c = (np.load(tmp_path / d / "messages.rank1.npy") for d in ("b", "c"))
+    assert b.shape == (40,) and np.array_equal(b, c) and np.isin(b, msgs.numpy()).all()
+    assert np.load(tmp_path / "b" / "results.rank1.npy").shape == (6, 4)
+
+
 def test_auto_route_with_gpu_calls_keeps_its_name():
     sw = {"auto_decoder_only": {"T1": {"slot_us_p50": 1.0}, "T1_calls": {"cpu": 10, "gpu": 3}}}
     out = bench.label_auto_route(sw)

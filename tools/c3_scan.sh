@@ -6,4 +6,6 @@ for nw in 0 1; do
     LDPC_HIP_NARROW=$nw timeout -k 10 120 python tools/time_variant.py $L $a || exit 1
   done
 done
-timeout -k 10 300 python bench.py --steps 5 --warmup 2 --cpu-baseline off > gpurun_out/bench_c4.log 2>&1
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
+timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --cpu-baseline off > "$OUT/bench_c4.log" 2>&1

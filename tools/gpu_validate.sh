@@ -10,6 +10,7 @@ rc=$?; echo "pytest rc=$rc"; tail -3 gpurun_out/pytest_gpu.log
 timeout -k 10 300 python -u -c 'import __graft_entry__ as g; g.smoke()' > gpurun_out/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -2 gpurun_out/smoke.log
 [ $rc -ne 0 ] && exit $rc
+BENCH_ARGS="--full ${BENCH_ARGS:-}"   # the extras (C3, C4, z sweep, HAL and software routes) run under --full only
 timeout -k 10 400 python -u bench.py --steps 50 --warmup 5 --cpu-baseline off ${BENCH_ARGS:-} \
   > gpurun_out/bench_quick.txt 2>&1
 rc=$?; echo "bench rc=$rc"; tail -c 600 gpurun_out/bench_quick.txt
