@@ -359,6 +359,78 @@ int ldpc_hip_dematch_decode_launch(ldpc_hip_plan* plan, const ldpc_hip_dematch_d
                                    const float* d_symbols, const float* d_noise_vars, int8_t* d_soft, uint8_t* d_out,
                                    ldpc_hip_cb_result* d_results, void* stream);
 
+/* ---- pseudo-random sequences: PUSCH descrambling ----------------------------------------
+ * pseudo_random_generator (include/srsran/phy/upper/sequence_generators/pseudo_random_generator.h): the length-31 Gold
+ * sequence of TS 38.211 5.2.1, c(n) = x1(n + 1600) ^ x2(n + 1600), x1(n + 31) = x1(n + 3) ^ x1(n) from x1 = 1,
+ * x2(n + 31) = x2(n + 3) ^ x2(n + 2) ^ x2(n + 1) ^ x2(n) from x2 = c_init. pusch_demodulator_impl initialises it with
+ * c_init = rnti * 2^15 + n_id (pusch_demodulator_impl.cpp:139-140) and reverts the scrambling on every block of LLRs
+ * after demodulate_soft (:289-293), before they reach pusch_codeblock_decoder.
+ * A generator state: bit i of x1 / x2 is x1 / x2 (1600 + offset + i), i < 31, `offset` bits into the sequence. */
+typedef struct {
+  uint32_t x1;
+  uint32_t x2;
+} ldpc_hip_prs_state;
+/* The state `offset` bits into the sequence of c_init (pseudo_random_generator::init then advance(offset)). Host
+ * only, no GPU needed; O(log offset): x^(1600 + offset) modulo each register's polynomial by square-and-multiply (the
+ * powers x^(2^k) are built at library load from the recurrences). The launches below call it once per segment or
+ * codeblock when they build their work items, never per LLR. */
+int ldpc_hip_prs_init(uint32_t c_init, uint64_t offset, ldpc_hip_prs_state* state);
+
+/* One segment of ldpc_hip_descramble_launch / ldpc_hip_scramble_bits_launch: `length` LLRs (or bits) that meet
+ * c(seq_offset .. seq_offset + length) of the sequence of c_init. */
+typedef struct {            /* 32 bytes */
+  uint64_t in_offset;       /* bytes from the input base  */
+  uint64_t out_offset;      /* bytes from the output base */
+  uint64_t seq_offset;      /* first sequence bit used    */
+  uint32_t length;          /* LLRs, or bits              */
+  uint32_t c_init;
+} ldpc_hip_prs_seg;
+
+/* Descrambles nof_segs segments of int8 LLRs on device buffers, asynchronously on `stream` (NULL = the context
+ * stream): out[i] = c(seq_offset + i) ? -in[i] : in[i], apply_xor(span<log_likelihood_ratio>)
+ * (pseudo_random_generator_impl.cpp:423-523). The device generates the sequence; the host computes each segment's
+ * start state only. LLRs are in [-127, 127]; -128 is outside the contract (as in the reference) and comes out as -128
+ * whatever the sequence bit. A segment may run in place (d_in == d_out, in_offset == out_offset); segments must not
+ * overlap otherwise. Any length and offsets; segments whose input and output addresses are 16-byte aligned take the
+ * vector path, others byte accesses. */
+int ldpc_hip_descramble_launch(ldpc_hip_ctx* ctx, uint32_t nof_segs, const ldpc_hip_prs_seg* segs, const int8_t* d_in,
+                               int8_t* d_out, void* stream);
+/* The packed form: apply_xor(bit_buffer) and, with d_in == NULL, generate(bit_buffer)
+ * (pseudo_random_generator_impl.cpp:84-144, 248-316). Bits are packed MSB first, length is in bits, the offsets in
+ * bytes; out = in ^ c. The bits of a segment's last byte beyond its length keep their input value (generate: zero). */
+int ldpc_hip_scramble_bits_launch(ldpc_hip_ctx* ctx, uint32_t nof_segs, const ldpc_hip_prs_seg* segs,
+                                  const uint8_t* d_in, uint8_t* d_out, void* stream);
+/* ldpc_hip_descramble_launch of one segment on host buffers (in == out allowed). */
+int ldpc_hip_descramble_sync(ldpc_hip_ctx* ctx, uint32_t c_init, uint64_t seq_offset, uint32_t n, const int8_t* in,
+                             int8_t* out);
+
+/* Scrambling of one codeblock for the dematcher: with enable != 0 the CB's rm_length LLRs meet
+ * c(seq_offset .. seq_offset + rm_length) of the sequence of c_init. Without UCI seq_offset is the sum of the rm_length
+ * of the codeword's earlier CBs (in general not a multiple of 32). */
+typedef struct {
+  uint32_t c_init;
+  uint8_t  enable;
+  uint8_t  pad[3];
+  uint64_t seq_offset;
+} ldpc_hip_scramble_desc;
+
+/* ldpc_hip_rate_dematch_launch (demod == NULL) or ldpc_hip_demod_dematch_launch (demod != NULL; d_llr / llr_offsets
+ * unused) with descrambling fused in: the dematcher descrambles CB i's LLRs (scr[i]) in its LDS staging, after they
+ * were loaded or demodulated and before the de-interleaving gather -- pusch_demodulator_impl.cpp:289-293 without an
+ * LLR round trip through HBM. An enabled CB requires rm_length <= 32768 (LDPC_HIP_EINVAL otherwise: descramble such a
+ * CB with ldpc_hip_descramble_launch first). scr == NULL: exactly the two existing entry points. */
+int ldpc_hip_rate_dematch_scr_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldpc_hip_dematch_desc* descs,
+                                     const int8_t* d_llr, const uint64_t* llr_offsets,
+                                     const ldpc_hip_demod_desc* demod, const float* d_symbols,
+                                     const float* d_noise_vars, const ldpc_hip_scramble_desc* scr, int8_t* d_soft,
+                                     const uint64_t* soft_offsets, void* stream);
+/* ldpc_hip_dematch_decode_launch with descrambling fused in (scr indexed like descs; NULL: no scrambling). */
+int ldpc_hip_dematch_decode_scr_launch(ldpc_hip_plan* plan, const ldpc_hip_dematch_desc* descs, const int8_t* d_llr,
+                                       const uint64_t* llr_offsets, const ldpc_hip_demod_desc* demod,
+                                       const float* d_symbols, const float* d_noise_vars,
+                                       const ldpc_hip_scramble_desc* scr, int8_t* d_soft, uint8_t* d_out,
+                                       ldpc_hip_cb_result* d_results, void* stream);
+
 /* ---- launch graphs: one submission per slot ---------------------------------------------------------------- */
 /* srsRAN runs the PUSCH decode chain once per slot with the same shape slot after slot (pusch_decoder_impl /
  * pusch_decoder_hw_impl call the decoder per codeblock and join per TB). Here the chain's *_launch calls on `stream`

@@ -38,6 +38,8 @@ EXPORTED_SYMBOLS = [
     "ldpc_hip_harq_repo_create", "ldpc_hip_harq_repo_release", "ldpc_hip_harq_repo_entry", "ldpc_hip_harq_repo_read",
     "ldpc_hip_open_harq", "ldpc_hip_harq_device_memory", "ldpc_hip_harq_capacity", "ldpc_hip_auto_device",
     "ldpc_hip_decode_work", "ldpc_hip_auto_min_work",
+    "ldpc_hip_prs_init", "ldpc_hip_descramble_launch", "ldpc_hip_scramble_bits_launch", "ldpc_hip_descramble_sync",
+    "ldpc_hip_rate_dematch_scr_launch", "ldpc_hip_dematch_decode_scr_launch",
 ]
 HARQ_STRIDE = 25344   # LDPC_HIP_HARQ_STRIDE
 
@@ -126,6 +128,26 @@ class DemodDesc(ctypes.Structure):
                 ("nof_symbols", ctypes.c_uint32), ("modulation", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3)]
 
 
+class PrsState(ctypes.Structure):
+    """ldpc_hip_prs_state (include/srsran_ldpc_hip.h)."""
+    _fields_ = [("x1", ctypes.c_uint32), ("x2", ctypes.c_uint32)]
+
+
+class PrsSeg(ctypes.Structure):
+    """ldpc_hip_prs_seg (include/srsran_ldpc_hip.h)."""
+    _fields_ = [("in_offset", ctypes.c_uint64), ("out_offset", ctypes.c_uint64), ("seq_offset", ctypes.c_uint64),
+                ("length", ctypes.c_uint32), ("c_init", ctypes.c_uint32)]
+
+
+class ScrambleDesc(ctypes.Structure):
+    """ldpc_hip_scramble_desc (include/srsran_ldpc_hip.h)."""
+    _fields_ = [("c_init", ctypes.c_uint32), ("enable", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3),
+                ("seq_offset", ctypes.c_uint64)]
+
+
+assert ctypes.sizeof(PrsState) == 8 and ctypes.sizeof(PrsSeg) == 32 and ctypes.sizeof(ScrambleDesc) == 16
+
+
 class TbResult(ctypes.Structure):
     _fields_ = [("tb_crc_ok", ctypes.c_uint8), ("written", ctypes.c_uint8), ("nof_cbs_ok", ctypes.c_uint16)]
 
@@ -190,6 +212,17 @@ def load():
                                               ctypes.POINTER(ctypes.c_uint64), P]),
         "ldpc_hip_dematch_decode_launch": (I, [P, ctypes.POINTER(DematchDesc), P, ctypes.POINTER(ctypes.c_uint64),
                                                ctypes.POINTER(DemodDesc), P, P, P, P, P, P]),
+        "ldpc_hip_prs_init": (I, [U32, ctypes.c_uint64, ctypes.POINTER(PrsState)]),
+        "ldpc_hip_descramble_launch": (I, [P, U32, ctypes.POINTER(PrsSeg), P, P, P]),
+        "ldpc_hip_scramble_bits_launch": (I, [P, U32, ctypes.POINTER(PrsSeg), P, P, P]),
+        "ldpc_hip_descramble_sync": (I, [P, U32, ctypes.c_uint64, U32, P, P]),
+        "ldpc_hip_rate_dematch_scr_launch": (I, [P, U32, ctypes.POINTER(DematchDesc), P,
+                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(DemodDesc), P, P,
+                                                 ctypes.POINTER(ScrambleDesc), P, ctypes.POINTER(ctypes.c_uint64),
+                                                 P]),
+        "ldpc_hip_dematch_decode_scr_launch": (I, [P, ctypes.POINTER(DematchDesc), P, ctypes.POINTER(ctypes.c_uint64),
+                                                   ctypes.POINTER(DemodDesc), P, P, ctypes.POINTER(ScrambleDesc), P,
+                                                   P, P, P]),
         "ldpc_hip_capture_begin": (I, [P, P]),
         "ldpc_hip_capture_end": (I, [P, P, ctypes.POINTER(P)]),
         "ldpc_hip_graph_launch": (I, [P, P]),

@@ -2652,7 +2652,7 @@ __global__ void __launch_bounds__(decode_max_threads<SPEC_ID>()) ldpc_dwq_decode
 {
   dwq_loop(a, [&](const dwq_item& it) __attribute__((always_inline)) {
     decode_cb<true, SPEC_ID>(it.cb, 0, nullptr, it.lay, it.llr_base, it.out_base, it.res_base, it.crc_tables, nullptr,
-                             it.dm);
+                             dm_plain(it.dm));
   });
 }
 

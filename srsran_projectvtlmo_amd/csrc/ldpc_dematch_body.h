@@ -136,6 +136,108 @@ __device__ __forceinline__ void dm_stage(const dematch_cb& d, unsigned nsym, con
   }
 }
 
+/* ---- pseudo-random sequence on the device (TS 38.211 5.2.1; ldpc_hip_device.h "pseudo-random sequence generator") --
+ * A thread owns a run of consecutive 32-bit sequence words of its segment: it jumps from the segment's start state to
+ * its first word (prs_jump_words: one polynomial jump per non-zero radix-32 digit of the word index, the polynomials
+ * from g_prs_jump, 1.5 KiB of constant data built at compile time from the recurrences) and then steps word by word
+ * (prs_next_word: the 64-bit extension of both states gives the 32 sequence bits and the states 32 bits on). */
+__device__ const prs_jump_table g_prs_jump = prs_make_jump_table();
+
+template <bool X2>
+__device__ __forceinline__ uint32_t prs_jump_dev(uint32_t s, uint32_t p)
+{
+  const uint64_t v = prs_extend<X2>(s);
+  uint32_t       r = 0;
+#pragma unroll
+  for (int k = 0; k != 31; ++k) {
+    r ^= static_cast<uint32_t>(v >> k) & (0U - ((p >> k) & 1U));
+  }
+  return r & PRS_MASK;
+}
+
+/* (x1, x2) advanced by j sequence words */
+__device__ __forceinline__ void prs_jump_words(uint32_t& x1, uint32_t& x2, uint32_t j)
+{
+  for (int m = 0; m != PRS_JUMP_DIGITS && (j >> (5 * m)) != 0U; ++m) {
+    const uint32_t d = (j >> (5 * m)) & 31U;
+    if (d != 0U) {
+      x1 = prs_jump_dev<false>(x1, g_prs_jump.p[0][m][d]);
+      x2 = prs_jump_dev<true>(x2, g_prs_jump.p[1][m][d]);
+    }
+  }
+}
+
+/* the 32 sequence bits at the states (bit i = c(n0 + i)); the states move 32 bits on */
+__device__ __forceinline__ uint32_t prs_next_word(uint32_t& x1, uint32_t& x2)
+{
+  const uint64_t v1 = prs_extend<false>(x1), v2 = prs_extend<true>(x2);
+  x1                = static_cast<uint32_t>(v1 >> 32) & PRS_MASK;
+  x2                = static_cast<uint32_t>(v2 >> 32) & PRS_MASK;
+  return static_cast<uint32_t>(v1) ^ static_cast<uint32_t>(v2);
+}
+
+/* Four LLRs (one per byte, the first in the low byte) negated where the matching bit of the low four bits of c is set:
+ * apply_xor on log_likelihood_ratio (pseudo_random_generator_impl.cpp:423-523). Byte-wise two's complement without
+ * carries between bytes; -128 (outside the LLR range, as in the reference) negates to itself. */
+__device__ __forceinline__ uint32_t prs_flip4(uint32_t x, uint32_t c)
+{
+  c &= 0xfU;
+  const uint32_t one = (c | (c << 7) | (c << 14) | (c << 21)) & 0x01010101U; /* 0x01 in the bytes to negate */
+  const uint32_t hi  = one << 7;
+  const uint32_t y   = x ^ (hi | (hi - one)); /* ~byte */
+  return ((y & 0x7f7f7f7fU) + one) ^ (y & 0x80808080U); /* + 1 */
+}
+
+/* the 32 LLRs of one sequence word, as two 16-byte vectors */
+__device__ __forceinline__ void prs_flip32(uint4& a, uint4& b, uint32_t w)
+{
+  a.x = prs_flip4(a.x, w);
+  a.y = prs_flip4(a.y, w >> 4);
+  a.z = prs_flip4(a.z, w >> 8);
+  a.w = prs_flip4(a.w, w >> 12);
+  b.x = prs_flip4(b.x, w >> 16);
+  b.y = prs_flip4(b.y, w >> 20);
+  b.z = prs_flip4(b.z, w >> 24);
+  b.w = prs_flip4(b.w, w >> 28);
+}
+
+/* The fused descrambler: the E LLRs staged in LDS (s_in, 16-byte aligned) descrambled in place from the CB's start
+ * state, the sequence words dealt out in equal runs over the workgroup (any width). The caller's barriers order it. */
+__device__ __forceinline__ void dm_descramble(int8_t* s_in, unsigned E, uint32_t x1, uint32_t x2)
+{
+  const unsigned nw  = (E + 31U) / 32U;
+  const unsigned run = (nw + blockDim.x - 1U) / blockDim.x;
+  const unsigned w0  = threadIdx.x * run;
+  if (w0 >= nw) {
+    return;
+  }
+  prs_jump_words(x1, x2, w0);
+  const unsigned w1 = min(w0 + run, nw);
+  for (unsigned w = w0; w < w1; ++w) {
+    const uint32_t c = prs_next_word(x1, x2);
+    if (32U * w + 32U <= E) {
+      uint4* p = reinterpret_cast<uint4*>(s_in + 32U * w);
+      uint4  a = p[0], b = p[1];
+      prs_flip32(a, b, c);
+      p[0] = a;
+      p[1] = b;
+    } else {
+      for (unsigned i = 32U * w; i < E; ++i) {
+        const int8_t v = s_in[i];
+        s_in[i]        = ((c >> (i & 31U)) & 1U) != 0U ? static_cast<int8_t>(-v) : v;
+      }
+    }
+  }
+}
+
+/* a work-queue item's dematch descriptor as the dematcher's (not scrambled) */
+__device__ __forceinline__ dematch_cb dm_plain(const dematch_cb_base& b)
+{
+  dematch_cb d{};
+  static_cast<dematch_cb_base&>(d) = b;
+  return d;
+}
+
 /* The dematcher's work for codeblock d: ldpc_rate_dematch_kernel's body, and the decode kernels' fused first phase
  * (ldpc_decode_body.h decode_cb, before the decoder prologue). s_in: DM_STAGE bytes of LDS staging; s_dtab: an LDS copy
  * of the demodulation tables (soft-demodulating form only). Uses the whole workgroup (any width); leaves the LDS and
@@ -239,6 +341,10 @@ __device__ __forceinline__ void dematch_body(const dematch_cb& d, const demod_ta
     }
     __syncthreads();
     DM_STAMP(1);
+  }
+  if (d.scr_x1 != 0U) { /* block-uniform; the host admits a scrambled CB only with E <= DM_STAGE, so it is staged */
+    dm_descramble(s_in, E, d.scr_x1, d.scr_x2);
+    __syncthreads();
   }
   const int8_t* src = (staged || d.sym != nullptr) ? static_cast<const int8_t*>(s_in) : in;
   auto sat_add = [](int a, int b) -> int8_t { /* log_likelihood_ratio::operator+ (llr.cpp:56-71) */

@@ -54,6 +54,8 @@ hipError_t launch_dematch(const dematch_cb* d_cbs, uint32_t n, const demod_table
 hipError_t configure_kernels(uint32_t max_lds);
 hipError_t launch_demodulate(const demod_seg* d_segs, uint32_t nseg, uint32_t nblocks, const demod_tables& tab,
                              const float* d_sym, const float* d_nv, int8_t* d_llr, hipStream_t stream);
+hipError_t launch_prs(const prs_seg* d_segs, uint32_t nseg, uint32_t nblocks, bool bits, const uint8_t* d_in,
+                      uint8_t* d_out, hipStream_t stream);
 } // namespace ldpc_hip
 
 using namespace ldpc_hip;
@@ -154,6 +156,45 @@ hipError_t upload_descs(dev_buffer& buf, desc_cache& last, const void* src, size
     last = desc_cache{};
   }
   return e;
+}
+
+/* ---- pseudo-random sequence generator, host side (ldpc_hip_device.h) ----
+ * x^(2^k) mod g for both registers, built at load by repeated squaring from x (the recurrences enter through the
+ * reduction x^31 = x^3 + 1 / x^3 + x^2 + x + 1). A jump by n bits is one polynomial jump per set bit of n. */
+struct prs_host_tables {
+  uint32_t pow2[2][64];
+  prs_host_tables()
+  {
+    for (int x = 0; x != 2; ++x) {
+      uint32_t p = 2;
+      for (int k = 0; k != 64; ++k) {
+        pow2[x][k] = p;
+        p          = prs_mulmod(p, p, x == 0 ? PRS_G1 : PRS_G2);
+      }
+    }
+  }
+};
+const prs_host_tables g_prs_host;
+
+template <bool X2>
+uint32_t prs_advance(uint32_t s, uint64_t n)
+{
+  for (int k = 0; n != 0; ++k, n >>= 1) {
+    if ((n & 1U) != 0U) {
+      s = prs_jump_poly<X2>(s, g_prs_host.pow2[X2 ? 1 : 0][k]);
+    }
+  }
+  return s;
+}
+
+/* the generator's state `offset` bits into the sequence of c_init: Nc = 1600 bits on from the initial registers,
+ * then offset (two jumps: 1600 + offset may not fit 64 bits) */
+ldpc_hip_prs_state prs_state_at(uint32_t c_init, uint64_t offset)
+{
+  ldpc_hip_prs_state st;
+  st.x1 = prs_advance<false>(prs_advance<false>(1U, PRS_NC), offset);
+  st.x2 = prs_advance<true>(prs_advance<true>(c_init & PRS_MASK, PRS_NC), offset);
+  return st;
 }
 
 int graph_slot(int bg, unsigned Z)
@@ -353,6 +394,8 @@ struct ldpc_hip_ctx {
   dev_buffer              d_encdesc; /* ldpc_hip_encode_launch descriptors */
   dev_buffer              d_rmdesc;  /* ldpc_hip_rate_match_launch descriptors */
   dev_buffer              d_dmsegs;  /* ldpc_hip_demodulate_launch segments */
+  dev_buffer              d_prssegs; /* ldpc_hip_descramble_launch / ldpc_hip_scramble_bits_launch segments */
+  desc_cache              c_prssegs;
   desc_cache              c_dmdesc, c_encdesc, c_rmdesc, c_tbdesc, c_dmsegs, c_tbaux; /* last uploads (upload_descs) */
   dev_buffer              d_tbaux;   /* ldpc_hip_tb_join_launch: TB << 8 | chunk per workgroup */
   dev_buffer              d_tbwork;  /* ldpc_hip_tb_join_launch: per-TB chunk CRCs + arrival counter (zero at rest) */
@@ -1228,50 +1271,28 @@ int ldpc_hip_decode_launch(ldpc_hip_plan* plan, const int8_t* d_llr, uint8_t* d_
 
 static int validate_dematch(ldpc_hip_ctx* ctx, const ldpc_hip_dematch_desc& d);
 
-int ldpc_hip_rate_dematch_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldpc_hip_dematch_desc* descs,
-                                 const int8_t* d_llr, const uint64_t* llr_offsets, int8_t* d_soft,
-                                 const uint64_t* soft_offsets, void* stream)
+/* the start state of a scrambled CB into its work item; false: the CB cannot be descrambled in the dematcher */
+static bool set_scrambling(dematch_cb& d, const ldpc_hip_scramble_desc* scr, uint32_t k)
 {
-  if (ctx == nullptr) {
-    return LDPC_HIP_EINVAL;
+  if (scr == nullptr || scr[k].enable == 0) {
+    return true;
   }
-  if (nof_cbs == 0) {
-    return LDPC_HIP_OK;
+  if (d.rm_length > DM_STAGE) {
+    return false;
   }
-  if (descs == nullptr || d_llr == nullptr || llr_offsets == nullptr || d_soft == nullptr || soft_offsets == nullptr) {
-    return ctx->fail(LDPC_HIP_EINVAL, "rate_dematch_launch: null argument");
-  }
-  std::vector<dematch_cb> dm(nof_cbs);
-  for (uint32_t i = 0; i != nof_cbs; ++i) {
-    const int r = validate_dematch(ctx, descs[i]);
-    if (r != LDPC_HIP_OK) {
-      return r;
-    }
-    const ldpc_hip_dematch_desc& s = descs[i];
-    dm[i]                          = dematch_cb{};
-    dm[i].llr                      = d_llr + llr_offsets[i];
-    dm[i].soft                     = d_soft + soft_offsets[i];
-    dm[i].cb_length                = s.cb_length;
-    dm[i].rm_length                = s.rm_length;
-    dm[i].Nref                     = s.Nref;
-    dm[i].nof_filler_bits          = s.nof_filler_bits;
-    dm[i].modulation_order         = s.modulation_order;
-    dm[i].rv                       = s.rv;
-    dm[i].new_data                 = s.new_data;
-  }
-  (void)hipSetDevice(ctx->device);
-  hipStream_t s = abi_stream(ctx->stream, stream);
-  hipError_t  e = upload_descs(ctx->d_dmdesc, ctx->c_dmdesc, dm.data(), nof_cbs * sizeof(dematch_cb), s);
-  if (e == hipSuccess) {
-    e = launch_dematch(ctx->d_dmdesc.as<dematch_cb>(), nof_cbs, ctx->dtab, s);
-  }
-  return e == hipSuccess ? LDPC_HIP_OK : ctx->hip_fail(e, "ldpc_rate_dematch_kernel launch");
+  const ldpc_hip_prs_state st = prs_state_at(scr[k].c_init, scr[k].seq_offset);
+  d.scr_x1                    = st.x1;
+  d.scr_x2                    = st.x2;
+  return true;
 }
+static const char* const k_scr_too_long = "scrambled codeblock with rm_length above 32768 cannot be descrambled in the "
+                                          "dematcher: descramble it with ldpc_hip_descramble_launch first";
 
-int ldpc_hip_demod_dematch_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldpc_hip_dematch_desc* descs,
-                                  const ldpc_hip_demod_desc* demod, const float* d_symbols,
-                                  const float* d_noise_vars, int8_t* d_soft, const uint64_t* soft_offsets,
-                                  void* stream)
+int ldpc_hip_rate_dematch_scr_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldpc_hip_dematch_desc* descs,
+                                     const int8_t* d_llr, const uint64_t* llr_offsets,
+                                     const ldpc_hip_demod_desc* demod, const float* d_symbols,
+                                     const float* d_noise_vars, const ldpc_hip_scramble_desc* scr, int8_t* d_soft,
+                                     const uint64_t* soft_offsets, void* stream)
 {
   if (ctx == nullptr) {
     return LDPC_HIP_EINVAL;
@@ -1279,8 +1300,13 @@ int ldpc_hip_demod_dematch_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldp
   if (nof_cbs == 0) {
     return LDPC_HIP_OK;
   }
-  if (descs == nullptr || demod == nullptr || d_symbols == nullptr || d_noise_vars == nullptr || d_soft == nullptr ||
-      soft_offsets == nullptr) {
+  if (demod == nullptr) {
+    if (descs == nullptr || d_llr == nullptr || llr_offsets == nullptr || d_soft == nullptr ||
+        soft_offsets == nullptr) {
+      return ctx->fail(LDPC_HIP_EINVAL, "rate_dematch_launch: null argument");
+    }
+  } else if (descs == nullptr || d_symbols == nullptr || d_noise_vars == nullptr || d_soft == nullptr ||
+             soft_offsets == nullptr) {
     return ctx->fail(LDPC_HIP_EINVAL, "demod_dematch_launch: null argument");
   }
   std::vector<dematch_cb> dm(nof_cbs);
@@ -1290,19 +1316,23 @@ int ldpc_hip_demod_dematch_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldp
       return r;
     }
     const ldpc_hip_dematch_desc& s = descs[i];
-    const ldpc_hip_demod_desc&   m = demod[i];
-    if (!valid_modulation(m.modulation) || bits_per_symbol(m.modulation) != s.modulation_order ||
-        static_cast<uint64_t>(m.nof_symbols) * s.modulation_order != s.rm_length) {
-      return ctx->fail(LDPC_HIP_EINVAL, "demod_dematch_launch: symbols x bits per symbol must equal rm_length");
+    dm[i]                          = dematch_cb{};
+    if (demod != nullptr) {
+      const ldpc_hip_demod_desc& m = demod[i];
+      if (!valid_modulation(m.modulation) || bits_per_symbol(m.modulation) != s.modulation_order ||
+          static_cast<uint64_t>(m.nof_symbols) * s.modulation_order != s.rm_length) {
+        return ctx->fail(LDPC_HIP_EINVAL, "demod_dematch_launch: symbols x bits per symbol must equal rm_length");
+      }
+      if (s.rm_length > DM_STAGE) {
+        return ctx->fail(LDPC_HIP_EINVAL, "demod_dematch_launch: rm_length above 32768 (use demodulate + dematch)");
+      }
+      dm[i].sym   = d_symbols + 2 * m.symbol_offset;
+      dm[i].nv    = d_noise_vars + m.noise_offset;
+      dm[i].demod = m.modulation;
+    } else {
+      dm[i].llr = d_llr + llr_offsets[i];
     }
-    if (s.rm_length > DM_STAGE) {
-      return ctx->fail(LDPC_HIP_EINVAL, "demod_dematch_launch: rm_length above 32768 (use demodulate + dematch)");
-    }
-    dm[i]                  = dematch_cb{};
     dm[i].soft             = d_soft + soft_offsets[i];
-    dm[i].sym              = d_symbols + 2 * m.symbol_offset;
-    dm[i].nv               = d_noise_vars + m.noise_offset;
-    dm[i].demod            = m.modulation;
     dm[i].cb_length        = s.cb_length;
     dm[i].rm_length        = s.rm_length;
     dm[i].Nref             = s.Nref;
@@ -1310,6 +1340,9 @@ int ldpc_hip_demod_dematch_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldp
     dm[i].modulation_order = s.modulation_order;
     dm[i].rv               = s.rv;
     dm[i].new_data         = s.new_data;
+    if (!set_scrambling(dm[i], scr, i)) {
+      return ctx->fail(LDPC_HIP_EINVAL, k_scr_too_long);
+    }
   }
   (void)hipSetDevice(ctx->device);
   hipStream_t s = abi_stream(ctx->stream, stream);
@@ -1317,7 +1350,29 @@ int ldpc_hip_demod_dematch_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldp
   if (e == hipSuccess) {
     e = launch_dematch(ctx->d_dmdesc.as<dematch_cb>(), nof_cbs, ctx->dtab, s);
   }
-  return e == hipSuccess ? LDPC_HIP_OK : ctx->hip_fail(e, "ldpc_rate_dematch_kernel launch (demodulating)");
+  return e == hipSuccess ? LDPC_HIP_OK
+                         : ctx->hip_fail(e, demod != nullptr ? "ldpc_rate_dematch_kernel launch (demodulating)"
+                                                             : "ldpc_rate_dematch_kernel launch");
+}
+
+int ldpc_hip_rate_dematch_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldpc_hip_dematch_desc* descs,
+                                 const int8_t* d_llr, const uint64_t* llr_offsets, int8_t* d_soft,
+                                 const uint64_t* soft_offsets, void* stream)
+{
+  return ldpc_hip_rate_dematch_scr_launch(ctx, nof_cbs, descs, d_llr, llr_offsets, nullptr, nullptr, nullptr, nullptr,
+                                          d_soft, soft_offsets, stream);
+}
+
+int ldpc_hip_demod_dematch_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldpc_hip_dematch_desc* descs,
+                                  const ldpc_hip_demod_desc* demod, const float* d_symbols,
+                                  const float* d_noise_vars, int8_t* d_soft, const uint64_t* soft_offsets,
+                                  void* stream)
+{
+  if (ctx != nullptr && nof_cbs != 0 && demod == nullptr) {
+    return ctx->fail(LDPC_HIP_EINVAL, "demod_dematch_launch: null argument");
+  }
+  return ldpc_hip_rate_dematch_scr_launch(ctx, nof_cbs, descs, nullptr, nullptr, demod, d_symbols, d_noise_vars,
+                                          nullptr, d_soft, soft_offsets, stream);
 }
 
 #ifdef LDPC_HIP_DIAG_CB
@@ -1337,6 +1392,16 @@ int ldpc_hip_dematch_decode_launch(ldpc_hip_plan* plan, const ldpc_hip_dematch_d
                                    const uint64_t* llr_offsets, const ldpc_hip_demod_desc* demod,
                                    const float* d_symbols, const float* d_noise_vars, int8_t* d_soft, uint8_t* d_out,
                                    ldpc_hip_cb_result* d_results, void* stream)
+{
+  return ldpc_hip_dematch_decode_scr_launch(plan, descs, d_llr, llr_offsets, demod, d_symbols, d_noise_vars, nullptr,
+                                            d_soft, d_out, d_results, stream);
+}
+
+int ldpc_hip_dematch_decode_scr_launch(ldpc_hip_plan* plan, const ldpc_hip_dematch_desc* descs, const int8_t* d_llr,
+                                       const uint64_t* llr_offsets, const ldpc_hip_demod_desc* demod,
+                                       const float* d_symbols, const float* d_noise_vars,
+                                       const ldpc_hip_scramble_desc* scr, int8_t* d_soft, uint8_t* d_out,
+                                       ldpc_hip_cb_result* d_results, void* stream)
 {
   if (plan == nullptr || plan->ctx == nullptr) {
     return LDPC_HIP_EINVAL;
@@ -1387,6 +1452,9 @@ int ldpc_hip_dematch_decode_launch(ldpc_hip_plan* plan, const ldpc_hip_dematch_d
     d.modulation_order = s.modulation_order;
     d.rv               = s.rv;
     d.new_data         = s.new_data;
+    if (!set_scrambling(d, scr, k)) {
+      return ctx->fail(LDPC_HIP_EINVAL, k_scr_too_long);
+    }
   }
   (void)hipSetDevice(ctx->device);
   const uint32_t   dm_lds = dm_fused_budget(dm.data(), dm.size());
@@ -2937,6 +3005,128 @@ int ldpc_hip_demodulate_sync(ldpc_hip_ctx* ctx, uint32_t nof_symbols, int modula
   if ((e = hipMemcpyAsync(llrs, ctx->d_llr.ptr, nllr, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
       (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
     return ctx->hip_fail(e, "demodulate_sync");
+  }
+  return LDPC_HIP_OK;
+}
+
+
+/* ---- pseudo-random sequences: descrambling and the packed-bit scrambler -------------------------------------------- */
+int ldpc_hip_prs_init(uint32_t c_init, uint64_t offset, ldpc_hip_prs_state* state)
+{
+  if (state == nullptr || (c_init & ~PRS_MASK) != 0U) {
+    return LDPC_HIP_EINVAL;
+  }
+  *state = prs_state_at(c_init, offset);
+  return LDPC_HIP_OK;
+}
+
+namespace {
+/* the segments as work items with their start states, and the launch; d_in == nullptr: generate (bits only) */
+int prs_segments(ldpc_hip_ctx* ctx, uint32_t nof_segs, const ldpc_hip_prs_seg* segs, bool bits, const uint8_t* d_in,
+                 uint8_t* d_out, hipStream_t s)
+{
+  std::vector<prs_seg> sg;
+  sg.reserve(nof_segs);
+  uint64_t blocks = 0;
+  for (uint32_t i = 0; i != nof_segs; ++i) {
+    const ldpc_hip_prs_seg& d = segs[i];
+    if ((d.c_init & ~PRS_MASK) != 0U) {
+      return ctx->fail(LDPC_HIP_EINVAL, "pseudo-random sequence: c_init above 31 bits");
+    }
+    if (d.length == 0) {
+      continue;
+    }
+    const ldpc_hip_prs_state st = prs_state_at(d.c_init, d.seq_offset);
+    prs_seg                  g{};
+    g.in_offset  = d_in != nullptr ? d.in_offset : PRS_NO_INPUT;
+    g.out_offset = d.out_offset;
+    g.length     = d.length;
+    g.block0     = static_cast<uint32_t>(blocks);
+    g.x1         = st.x1;
+    g.x2         = st.x2;
+    sg.push_back(g);
+    const uint64_t words = (static_cast<uint64_t>(d.length) + 31U) / 32U;
+    blocks += (words + PRS_BLOCK * PRS_WORDS - 1U) / (PRS_BLOCK * PRS_WORDS);
+    if (blocks > 0x7fffffffULL) {
+      return ctx->fail(LDPC_HIP_EINVAL, "pseudo-random sequence: too many LLRs or bits for one launch");
+    }
+  }
+  if (sg.empty()) {
+    return LDPC_HIP_OK;
+  }
+  hipError_t e = upload_descs(ctx->d_prssegs, ctx->c_prssegs, sg.data(), sg.size() * sizeof(prs_seg), s);
+  if (e == hipSuccess) {
+    e = launch_prs(ctx->d_prssegs.as<prs_seg>(), static_cast<uint32_t>(sg.size()), static_cast<uint32_t>(blocks), bits,
+                   d_in, d_out, s);
+  }
+  return e == hipSuccess ? LDPC_HIP_OK : ctx->hip_fail(e, "ldpc_prs_kernel launch");
+}
+} // namespace
+
+int ldpc_hip_descramble_launch(ldpc_hip_ctx* ctx, uint32_t nof_segs, const ldpc_hip_prs_seg* segs, const int8_t* d_in,
+                               int8_t* d_out, void* stream)
+{
+  if (ctx == nullptr) {
+    return LDPC_HIP_EINVAL;
+  }
+  if (nof_segs == 0) {
+    return LDPC_HIP_OK;
+  }
+  if (segs == nullptr || d_in == nullptr || d_out == nullptr) {
+    return ctx->fail(LDPC_HIP_EINVAL, "descramble_launch: null argument");
+  }
+  (void)hipSetDevice(ctx->device);
+  return prs_segments(ctx, nof_segs, segs, false, reinterpret_cast<const uint8_t*>(d_in),
+                      reinterpret_cast<uint8_t*>(d_out), abi_stream(ctx->stream, stream));
+}
+
+int ldpc_hip_scramble_bits_launch(ldpc_hip_ctx* ctx, uint32_t nof_segs, const ldpc_hip_prs_seg* segs,
+                                  const uint8_t* d_in, uint8_t* d_out, void* stream)
+{
+  if (ctx == nullptr) {
+    return LDPC_HIP_EINVAL;
+  }
+  if (nof_segs == 0) {
+    return LDPC_HIP_OK;
+  }
+  if (segs == nullptr || d_out == nullptr) {
+    return ctx->fail(LDPC_HIP_EINVAL, "scramble_bits_launch: null argument");
+  }
+  (void)hipSetDevice(ctx->device);
+  return prs_segments(ctx, nof_segs, segs, true, d_in, d_out, abi_stream(ctx->stream, stream));
+}
+
+int ldpc_hip_descramble_sync(ldpc_hip_ctx* ctx, uint32_t c_init, uint64_t seq_offset, uint32_t n, const int8_t* in,
+                             int8_t* out)
+{
+  if (ctx == nullptr) {
+    return LDPC_HIP_EINVAL;
+  }
+  if (n == 0) {
+    return LDPC_HIP_OK;
+  }
+  if (in == nullptr || out == nullptr) {
+    return ctx->fail(LDPC_HIP_EINVAL, "descramble_sync: null argument");
+  }
+  (void)hipSetDevice(ctx->device);
+  hipError_t e;
+  if ((e = ctx->d_llr.reserve(n)) != hipSuccess) {
+    return ctx->hip_fail(e, "hipMalloc(descramble)");
+  }
+  if ((e = hipMemcpyAsync(ctx->d_llr.ptr, in, n, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) {
+    return ctx->hip_fail(e, "hipMemcpyAsync(descramble in)");
+  }
+  ldpc_hip_prs_seg d{};
+  d.seq_offset = seq_offset;
+  d.length     = n;
+  d.c_init     = c_init;
+  const int r  = prs_segments(ctx, 1, &d, false, ctx->d_llr.as<uint8_t>(), ctx->d_llr.as<uint8_t>(), ctx->stream);
+  if (r != LDPC_HIP_OK) {
+    return r;
+  }
+  if ((e = hipMemcpyAsync(out, ctx->d_llr.ptr, n, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
+    return ctx->hip_fail(e, "descramble_sync");
   }
   return LDPC_HIP_OK;
 }

@@ -194,8 +194,9 @@ constexpr unsigned DM_STAGE   = 32768;
 
 /* One rate-dematch work item. llr / soft are absolute device pointers. With sym != nullptr the E LLRs are not read
  * from llr but produced in LDS by soft-demodulating the CB's E / Qm symbols (sym, noise variances nv, modulation
- * demod = modulation_scheme value; E <= DM_STAGE): ldpc_hip_demod_dematch_launch. */
-struct dematch_cb {
+ * demod = modulation_scheme value; E <= DM_STAGE): ldpc_hip_demod_dematch_launch. dematch_cb_base is the part a
+ * work-queue item carries (dwq_item: the HAL queue and the one-CB calls take descrambled LLRs). */
+struct dematch_cb_base {
   const int8_t* llr;
   int8_t*       soft;
   const float*  sym; /* interleaved (re, im) */
@@ -209,6 +210,110 @@ struct dematch_cb {
   uint8_t       new_data;
   uint8_t       demod;
   uint32_t      stage_bytes; /* LDS staging the launch reserved for the LLRs (E <= stage_bytes is staged); 0: DM_STAGE */
+};
+/* The launched kernels' work item: with scr_x1 != 0 the CB's E LLRs are scrambled (TS 38.211 6.3.1.1) and scr_x1 /
+ * scr_x2 are the generator's state at the CB's first LLR (prs_state_at, computed on the host when the item is built);
+ * the dematcher descrambles them in its LDS staging (E <= DM_STAGE). An x1 state is never zero, so 0 = not scrambled. */
+struct dematch_cb : dematch_cb_base {
+  uint32_t scr_x1;
+  uint32_t scr_x2;
+};
+static_assert(sizeof(dematch_cb_base) == 56 && sizeof(dematch_cb) == 64, "dematch work item layout");
+
+/* ---- pseudo-random sequence generator (TS 38.211 5.2.1; pseudo_random_generator_impl) -----------------------------
+ * c(n) = x1(n + 1600) ^ x2(n + 1600), x1(n + 31) = x1(n + 3) ^ x1(n), x2(n + 31) = x2(n + 3) ^ x2(n + 2) ^ x2(n + 1) ^
+ * x2(n). A state is 31 bits of one register's sequence, bit i = x(1600 + offset + i). Both registers satisfy a linear
+ * recurrence, so for any N with x^N mod g(x) = sum_k p_k x^k (g the register's characteristic polynomial) the sequence
+ * obeys x(n + N) = sum_k p_k x(n + k): a jump by N bits is the XOR of the state's 61-bit extension shifted by every k
+ * with p_k set (prs_jump_poly). The polynomials x^N mod g come from square-and-multiply (prs_mulmod), on the host for
+ * ldpc_hip_prs_init and at compile time for the device's table (prs_jump_table). */
+constexpr uint32_t PRS_G1    = 0x9U;  /* x^31 = x^3 + 1             */
+constexpr uint32_t PRS_G2    = 0xfU;  /* x^31 = x^3 + x^2 + x + 1   */
+constexpr uint32_t PRS_MASK  = 0x7fffffffU;
+constexpr uint32_t PRS_NC    = 1600;
+
+/* a(x) b(x) mod g(x) over GF(2), g = x^31 + (low terms g_low); a, b of degree < 31 */
+constexpr uint32_t prs_mulmod(uint32_t a, uint32_t b, uint32_t g_low)
+{
+  uint32_t r = 0;
+  for (int i = 30; i >= 0; --i) {
+    r <<= 1;
+    if ((r >> 31) != 0U) {
+      r = (r & PRS_MASK) ^ g_low;
+    }
+    if (((b >> i) & 1U) != 0U) {
+      r ^= a;
+    }
+  }
+  return r;
+}
+
+/* The 31-bit state s extended to the register's next 64 sequence bits (bit i = x(n0 + i)): taps = 3 for x1 (x(n+31) =
+ * x(n+3) ^ x(n)), taps = 0 for x2 (all of x(n+3) .. x(n)). Two word-parallel steps: 28 new bits, then 5. */
+template <bool X2>
+constexpr uint64_t prs_extend(uint32_t s)
+{
+  uint64_t v = s & PRS_MASK;
+  uint64_t f = X2 ? (v ^ (v >> 1) ^ (v >> 2) ^ (v >> 3)) : (v ^ (v >> 3));
+  v |= (f & 0xfffffffULL) << 31;
+  f = X2 ? (v ^ (v >> 1) ^ (v >> 2) ^ (v >> 3)) : (v ^ (v >> 3));
+  v |= ((f >> 28) & 0x1fULL) << 59;
+  return v;
+}
+
+/* the state N bits on, p = x^N mod g */
+template <bool X2>
+constexpr uint32_t prs_jump_poly(uint32_t s, uint32_t p)
+{
+  const uint64_t v = prs_extend<X2>(s);
+  uint32_t       r = 0;
+  for (int k = 0; k != 31; ++k) {
+    r ^= static_cast<uint32_t>(v >> k) & (0U - ((p >> k) & 1U));
+  }
+  return r & PRS_MASK;
+}
+
+/* The device's jump table: a thread reaches sequence word j (32 bits each) of its segment from the segment's start
+ * state by one jump per non-zero radix-32 digit of j: p[x][m][d] = x^(32 d 32^m) mod g. 6 digits cover 2^30 words. */
+constexpr int PRS_JUMP_DIGITS = 6;
+struct prs_jump_table {
+  uint32_t p[2][PRS_JUMP_DIGITS][32];
+};
+constexpr prs_jump_table prs_make_jump_table()
+{
+  prs_jump_table t{};
+  for (int x = 0; x != 2; ++x) {
+    const uint32_t g    = x == 0 ? PRS_G1 : PRS_G2;
+    uint32_t       base = 2; /* x^1 */
+    for (int i = 0; i != 5; ++i) {
+      base = prs_mulmod(base, base, g); /* x^32 */
+    }
+    for (int m = 0; m != PRS_JUMP_DIGITS; ++m) {
+      t.p[x][m][0] = 1;
+      for (int d = 1; d != 32; ++d) {
+        t.p[x][m][d] = prs_mulmod(t.p[x][m][d - 1], base, g);
+      }
+      for (int i = 0; i != 5; ++i) {
+        base = prs_mulmod(base, base, g); /* x^(32 32^(m+1)) */
+      }
+    }
+  }
+  return t;
+}
+
+/* One segment of the stand-alone descrambler / packed-bit scrambler (ldpc_prs_kernel): length LLRs (or bits) from the
+ * start state (x1, x2). Blocks [block0, block0 + ceil(words / (PRS_BLOCK PRS_WORDS))) of the launch work on it, a
+ * thread on PRS_WORDS consecutive 32-bit sequence words. in_offset = PRS_NO_INPUT: generate (the input reads as 0). */
+constexpr int      PRS_BLOCK    = 256;
+constexpr int      PRS_WORDS    = 4;
+constexpr uint64_t PRS_NO_INPUT = ~0ULL;
+struct prs_seg {
+  uint64_t in_offset;
+  uint64_t out_offset;
+  uint32_t length;
+  uint32_t block0;
+  uint32_t x1;
+  uint32_t x2;
 };
 
 /* One soft-demodulation segment (ldpc_hip_demodulate_launch): nof_symbols symbols of one modulation. Blocks
@@ -244,7 +349,7 @@ constexpr uint32_t DM_FUSED_LDS = DM_STAGE + ((sizeof(demod_tables) + 15U) & ~15
 struct dwq_item {
   dec_cb              cb;
   lds_layout          lay;
-  dematch_cb          dm;   /* dm.soft != nullptr: the dematcher runs first (fused) */
+  dematch_cb_base     dm;   /* dm.soft != nullptr: the dematcher runs first (fused); never scrambled */
   const int8_t*       llr_base;
   uint8_t*            out_base;
   ldpc_hip_cb_result* res_base;

@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(DM_THREADS) ldpc_dwq_dematch_kernel(dwq_args a
 {
   dwq_loop(a, [&](const dwq_item& it) __attribute__((always_inline)) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    dematch_body(it.dm, *reinterpret_cast<const demod_tables*>(it.crc_tables + DTAB_OFFSET),
+    dematch_body(dm_plain(it.dm), *reinterpret_cast<const demod_tables*>(it.crc_tables + DTAB_OFFSET),
                  reinterpret_cast<int8_t*>(smem), *reinterpret_cast<demod_tables*>(smem + DM_STAGE));
   });
 }
@@ -1101,6 +1101,92 @@ hipError_t launch_demodulate(const demod_seg* d_segs, uint32_t nseg, uint32_t nb
   }
   hipLaunchKernelGGL(ldpc_demodulate_kernel, dim3(nblocks), dim3(DEMOD_BLOCK), 0, stream, d_segs, nseg, tab,
                      reinterpret_cast<const float2*>(d_sym), d_nv, d_llr);
+  return hipGetLastError();
+}
+
+/* ---- PUSCH descrambling and the packed-bit scrambler (pseudo_random_generator_impl.cpp apply_xor / generate) --------
+ * One thread per PRS_WORDS consecutive 32-bit sequence words of a segment (ldpc_dematch_body.h prs_jump_words, then
+ * prs_next_word per word). BITS = false: a word covers 32 int8 LLRs, out = c ? -in : in (-128 stays -128); two 16-byte
+ * loads and stores per whole word when the segment's input and output addresses are 16-byte aligned, byte accesses
+ * for other segments and for the last, partial word. BITS = true: a word covers 4 bytes of bits packed MSB first,
+ * out = in ^ c, the input read as zero for a generating segment; the bits of the last byte beyond the segment's length
+ * keep their input value. A thread reads its bytes before it writes them, so a segment may run in place. */
+template <bool BITS>
+__global__ void __launch_bounds__(PRS_BLOCK)
+    ldpc_prs_kernel(const prs_seg* __restrict__ segs, uint32_t nseg, const uint8_t* in_base, uint8_t* out_base)
+{
+  uint32_t lo = 0, hi = nseg; /* this block's segment: the last one with block0 <= blockIdx.x */
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (segs[mid].block0 <= blockIdx.x) {
+      lo = mid;
+    } else {
+      hi = mid;
+    }
+  }
+  const prs_seg  sg = segs[lo];
+  const uint32_t nw = sg.length / 32U + (sg.length % 32U != 0U ? 1U : 0U);
+  const uint32_t w0 = ((blockIdx.x - sg.block0) * PRS_BLOCK + threadIdx.x) * PRS_WORDS;
+  if (w0 >= nw) {
+    return;
+  }
+  uint32_t x1 = sg.x1, x2 = sg.x2;
+  prs_jump_words(x1, x2, w0);
+  const bool     gen = sg.in_offset == PRS_NO_INPUT;
+  const uint8_t* in  = gen ? nullptr : in_base + sg.in_offset;
+  uint8_t*       out = out_base + sg.out_offset;
+  const uint32_t w1  = min(w0 + PRS_WORDS, nw);
+  if constexpr (!BITS) {
+    const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15U) == 0; /* uniform */
+    for (uint32_t w = w0; w < w1; ++w) {
+      const uint32_t c = prs_next_word(x1, x2);
+      const uint64_t b = static_cast<uint64_t>(w) * 32U;
+      if (vec && b + 32U <= sg.length) {
+        uint4 a0 = reinterpret_cast<const uint4*>(in + b)[0], a1 = reinterpret_cast<const uint4*>(in + b)[1];
+        prs_flip32(a0, a1, c);
+        reinterpret_cast<uint4*>(out + b)[0] = a0;
+        reinterpret_cast<uint4*>(out + b)[1] = a1;
+      } else {
+        const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(32U), sg.length - b));
+        for (uint32_t i = 0; i < n; ++i) {
+          const int8_t v = static_cast<int8_t>(in[b + i]);
+          out[b + i]     = static_cast<uint8_t>(((c >> i) & 1U) != 0U ? static_cast<int8_t>(-v) : v);
+        }
+      }
+    }
+  } else {
+    const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 3U) == 0; /* uniform */
+    for (uint32_t w = w0; w < w1; ++w) {
+      /* sequence bit i of the word belongs in byte i / 8 at bit 7 - i % 8 */
+      const uint32_t c = __builtin_bswap32(__builtin_bitreverse32(prs_next_word(x1, x2))); /* byte k in bits 8k.. */
+      const uint64_t b = static_cast<uint64_t>(w) * 4U;
+      if (vec && static_cast<uint64_t>(w) * 32U + 32U <= sg.length) {
+        const uint32_t v = gen ? 0U : *reinterpret_cast<const uint32_t*>(in + b);
+        *reinterpret_cast<uint32_t*>(out + b) = v ^ c;
+      } else {
+        const uint32_t bits = static_cast<uint32_t>(min(static_cast<uint64_t>(32U), sg.length - 32U * w));
+        for (uint32_t k = 0; 8U * k < bits; ++k) {
+          const uint32_t nb   = min(8U, bits - 8U * k);
+          const uint32_t keep = (0xff00U >> nb) & 0xffU; /* the byte's first nb bits (MSB first) */
+          const uint32_t v    = gen ? 0U : in[b + k];
+          out[b + k]          = static_cast<uint8_t>(v ^ ((c >> (8U * k)) & keep));
+        }
+      }
+    }
+  }
+}
+
+hipError_t launch_prs(const prs_seg* d_segs, uint32_t nseg, uint32_t nblocks, bool bits, const uint8_t* d_in,
+                      uint8_t* d_out, hipStream_t stream)
+{
+  if (nblocks == 0) {
+    return hipSuccess;
+  }
+  if (bits) {
+    hipLaunchKernelGGL(ldpc_prs_kernel<true>, dim3(nblocks), dim3(PRS_BLOCK), 0, stream, d_segs, nseg, d_in, d_out);
+  } else {
+    hipLaunchKernelGGL(ldpc_prs_kernel<false>, dim3(nblocks), dim3(PRS_BLOCK), 0, stream, d_segs, nseg, d_in, d_out);
+  }
   return hipGetLastError();
 }
 

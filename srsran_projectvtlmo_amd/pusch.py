@@ -74,6 +74,8 @@ class tb_slot_spec:
     max_iterations: int = 6
     use_early_stop: bool = True
     modulation: int = -1         # modulation_scheme of the codeword's symbols (upload_symbols); -1: the one of Qm
+    rnti: int = -1               # >= 0: the codeword is scrambled with c_init = rnti * 2^15 + n_id (TS 38.211 6.3.1.1,
+    n_id: int = 0                # pusch_demodulator_impl.cpp:139-140); -1: the LLRs / symbols are not scrambled
 
     @property
     def modulation_scheme(self) -> int:
@@ -88,10 +90,28 @@ class tb_slot_spec:
         return 16 if self.tbs <= 3824 else 24     # pusch_decoder_impl select_crc / TS 38.212 7.2.1
 
 
+def slot_scramble_entries(tbs: Sequence[tb_slot_spec]):
+    """Per codeblock of the slot, in SlotPipeline's CB order: None (its TB is not scrambled) or (c_init, seq_offset),
+    seq_offset the sum of the rm_lengths of the codeword's earlier CBs (no UCI in the codeword). Host logic only."""
+    from .sequence_generators import pusch_c_init
+    out = []
+    for tb in tbs:
+        pos = 0
+        for E in tb.rm_lengths:
+            out.append((pusch_c_init(tb.rnti, tb.n_id), pos) if tb.rnti >= 0 else None)
+            pos += E
+    return out
+
+
+DM_STAGE = 32768     # largest rm_length the dematcher stages in LDS: fused demodulation / descrambling up to it
+
+
 class SlotPipeline:
     """The PUSCH decode path of one slot on the device, mirroring pusch_decoder_impl (pusch_decoder_impl.cpp:
     309-497) with pusch_codeblock_decoder (pusch_codeblock_decoder.cpp:35-71) per CB:
 
+      [descramble every scrambled CB's LLRs (pusch_demodulator_impl.cpp:289-293): inside the dematcher, or for a CB
+       it cannot stage (E > 32768, or demodulation not fused) by ldpc_hip_descramble_launch before it]
       rate-dematch every CB's E LLRs into its N-LLR soft buffer (HARQ state, kept in HBM across launches)
       -> decode every CB (CRC early stop with CRC24B, or the TB CRC for a single-CB TB; or CRC after decoding)
       -> join each TB's codeblocks and check the TB CRC24A.
@@ -152,13 +172,33 @@ class SlotPipeline:
         self.nof_cbs = len(dec)
         self._dm = (DematchDesc * max(1, len(dm)))(*dm)
         self._llr_off = (ctypes.c_uint64 * max(1, len(llr_off)))(*llr_off)
+        # scrambling: per CB (c_init, sequence offset). CBs the dematcher stages are descrambled inside it (_scr); the
+        # longer ones of uploaded LLRs go through ldpc_hip_descramble_launch into a clear copy behind the slot's LLRs
+        # (out of place: the uploaded LLRs stay scrambled, so launch() and a graph replay can run again), and the
+        # dematcher reads those CBs there (_llr_off_clear). Demodulated LLRs (_scr_inplace) are descrambled in place.
+        from . import sequence_generators as sg
+        self.scramble_entries = slot_scramble_entries(self.tbs)
+        self.scrambled = any(e is not None for e in self.scramble_entries)
+        Es = [d.rm_length for d in dm]
+        self._scr = sg.scramble_descriptors([e if E <= DM_STAGE else None
+                                             for e, E in zip(self.scramble_entries, Es)])
+        long_cbs = [i for i, (e, E) in enumerate(zip(self.scramble_entries, Es)) if e is not None and E > DM_STAGE]
+        self._scr_long = sg.prs_descriptors([sg.prs_segment(Es[i], *self.scramble_entries[i], llr_off[i],
+                                                            lo + llr_off[i]) for i in long_cbs])
+        self._scr_long_n = len(long_cbs)
+        clear_off = [o + lo if i in long_cbs else o for i, o in enumerate(llr_off)]
+        self._llr_off_clear = (ctypes.c_uint64 * max(1, len(llr_off)))(*clear_off)
+        every = [i for i, e in enumerate(self.scramble_entries) if e is not None]
+        self._scr_inplace = sg.prs_descriptors([sg.prs_segment(Es[i], *self.scramble_entries[i], llr_off[i],
+                                                               llr_off[i]) for i in every])
+        self._scr_inplace_n = len(every)
         self._soft_off = (ctypes.c_uint64 * max(1, len(soft_off)))(*soft_off)
         self.plan = cc.DecodePlan(ctx, dec)
         self.joins = joins
         self._tb_arr = tb_join_descriptors(joins)
         dev = torch.device("cuda", ctx.device)
         self.h_llr = torch.zeros(max(16, lo), dtype=torch.int8).pin_memory()
-        self.d_llr = torch.zeros(max(16, lo), dtype=torch.int8, device=dev)
+        self.d_llr = torch.zeros(max(16, lo * (2 if long_cbs else 1)), dtype=torch.int8, device=dev)
         self.d_soft = torch.zeros(max(16, so), dtype=torch.int8, device=dev)     # HARQ soft buffers
         self.d_out = torch.zeros(max(16, oo), dtype=torch.uint8, device=dev)
         self.d_res = torch.zeros(max(1, len(dec)) * 4, dtype=torch.uint8, device=dev)
@@ -211,14 +251,15 @@ class SlotPipeline:
         self.from_symbols = True
 
     def upload(self, llrs_per_tb, stream=None) -> None:
-        """llrs_per_tb[i][r]: int8 E-LLRs of CB r of TB i (host arrays). One pinned host-to-device copy."""
+        """llrs_per_tb[i][r]: int8 E-LLRs of CB r of TB i (host arrays); those of a TB with rnti >= 0 are still
+        scrambled. One pinned host-to-device copy."""
         h = self.h_llr.numpy()
         for offs, llrs in zip(self.cb_llr_offsets, llrs_per_tb):
             for off, l in zip(offs, llrs):
                 h[off:off + l.size] = l
         # blocking: the launch may go to the context's own non-blocking stream, which the default stream's copy does
         # not order (a non-blocking copy here once let a launch read the LLRs before they had landed)
-        self.d_llr.copy_(self.h_llr)
+        self.d_llr[: self.h_llr.numel()].copy_(self.h_llr)
 
     def upload_device(self, llrs_per_tb) -> None:
         """As upload(), from per-CB device int8 tensors (e.g. srsran_projectvtlmo_amd.synth): device-to-device."""
@@ -233,35 +274,52 @@ class SlotPipeline:
         fuse_dematch is off). CBs whose CRC passed in an earlier launch are only dematched (pusch_decoder_impl.cpp:
         336-346); new-data TBs decode every CB."""
         L, c = self.ctx.lib, self.ctx.handle
+        from . import channel_modulation, sequence_generators
+        sym = self.from_symbols and self.fuse_demod           # symbols demodulated inside the dematcher
+        scr, llr_off = None, self._llr_off
+        if self.from_symbols and not self.fuse_demod:
+            channel_modulation.demodulate_launch(self.ctx, self._demod_arr, self.d_sym.data_ptr(),
+                                                 self.d_nv.data_ptr(), self.d_llr.data_ptr(), stream,
+                                                 n=len(self.demod_segments))
+            if self.scrambled:
+                # between demodulation and dematching, in place (pusch_demodulator_impl.cpp:289-293)
+                sequence_generators.descramble_launch(self.ctx, self._scr_inplace, self.d_llr.data_ptr(),
+                                                      self.d_llr.data_ptr(), stream, n=self._scr_inplace_n)
+        elif self.scrambled:
+            scr = self._scr
+            if self._scr_long_n and not self.from_symbols:
+                sequence_generators.descramble_launch(self.ctx, self._scr_long, self.d_llr.data_ptr(),
+                                                      self.d_llr.data_ptr(), stream, n=self._scr_long_n)
+                llr_off = self._llr_off_clear
         if self.fuse_dematch:
-            # each decoder workgroup dematches (and, from symbols, demodulates) its CB first: one launch
-            if self.from_symbols and not self.fuse_demod:
-                from . import channel_modulation
-                channel_modulation.demodulate_launch(self.ctx, self._demod_arr, self.d_sym.data_ptr(),
-                                                     self.d_nv.data_ptr(), self.d_llr.data_ptr(), stream,
-                                                     n=len(self.demod_segments))
-            sym = self.from_symbols and self.fuse_demod
-            rc = L.ldpc_hip_dematch_decode_launch(
-                self.plan.handle, self._dm, None if sym else self.d_llr.data_ptr(), None if sym else self._llr_off,
-                self._demod_arr if sym else None, self.d_sym.data_ptr() if sym else None,
-                self.d_nv.data_ptr() if sym else None, self.d_soft.data_ptr(), self.d_out.data_ptr(),
-                self.d_res.data_ptr(), _lib.stream_arg(stream))
-            _lib.check(c, rc, "ldpc_hip_dematch_decode_launch")
+            # each decoder workgroup dematches (and, from symbols, demodulates; scrambled, descrambles) its CB first
+            args = (self.plan.handle, self._dm, None if sym else self.d_llr.data_ptr(), None if sym else llr_off,
+                    self._demod_arr if sym else None, self.d_sym.data_ptr() if sym else None,
+                    self.d_nv.data_ptr() if sym else None)
+            tail = (self.d_soft.data_ptr(), self.d_out.data_ptr(), self.d_res.data_ptr(), _lib.stream_arg(stream))
+            if scr is not None:
+                rc = L.ldpc_hip_dematch_decode_scr_launch(*args, scr, *tail)
+                _lib.check(c, rc, "ldpc_hip_dematch_decode_scr_launch")
+            else:
+                rc = L.ldpc_hip_dematch_decode_launch(*args, *tail)
+                _lib.check(c, rc, "ldpc_hip_dematch_decode_launch")
             tb_join_launch(self.ctx, self._tb_arr, self.d_out.data_ptr(), self.d_res.data_ptr(), self.d_tb.data_ptr(),
                            self.d_tbres.data_ptr(), stream, n=len(self.joins))
             return
-        if self.from_symbols and self.fuse_demod:
+        if scr is not None:
+            rc = L.ldpc_hip_rate_dematch_scr_launch(
+                c, self.nof_cbs, self._dm, None if sym else self.d_llr.data_ptr(), None if sym else llr_off,
+                self._demod_arr if sym else None, self.d_sym.data_ptr() if sym else None,
+                self.d_nv.data_ptr() if sym else None, scr, self.d_soft.data_ptr(), self._soft_off,
+                _lib.stream_arg(stream))
+            _lib.check(c, rc, "ldpc_hip_rate_dematch_scr_launch")
+        elif sym:
             # each CB's symbols demodulated straight into the dematcher's LDS staging (no LLR round trip)
             rc = L.ldpc_hip_demod_dematch_launch(c, self.nof_cbs, self._dm, self._demod_arr, self.d_sym.data_ptr(),
                                                  self.d_nv.data_ptr(), self.d_soft.data_ptr(), self._soft_off,
                                                  _lib.stream_arg(stream))
             _lib.check(c, rc, "ldpc_hip_demod_dematch_launch")
         else:
-            if self.from_symbols:
-                from . import channel_modulation
-                channel_modulation.demodulate_launch(self.ctx, self._demod_arr, self.d_sym.data_ptr(),
-                                                     self.d_nv.data_ptr(), self.d_llr.data_ptr(), stream,
-                                                     n=len(self.demod_segments))
             rc = L.ldpc_hip_rate_dematch_launch(c, self.nof_cbs, self._dm, self.d_llr.data_ptr(), self._llr_off,
                                                 self.d_soft.data_ptr(), self._soft_off, _lib.stream_arg(stream))
             _lib.check(c, rc, "ldpc_hip_rate_dematch_launch")

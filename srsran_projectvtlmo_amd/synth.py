@@ -99,9 +99,10 @@ def modulate(bits, mod: int):
 
 def rate_matched_symbols(ctx: _lib.Context, bg: int, Z: int, msgs_bits: np.ndarray, rm_lengths: Sequence[int],
                          Qm: int, rv: int, nof_filler_bits: int, noise_var: float, seed: int, Nref: int = 0,
-                         stream: int = 0):
+                         stream: int = 0, c_init: int = -1):
     """Encode and rate-match every CB, concatenate the codeword, modulate (TS 38.211 §5.1) and add complex AWGN of
-    variance noise_var: (device complex64 symbols, device float32 noise variances) of the TB's codeword."""
+    variance noise_var: (device complex64 symbols, device float32 noise variances) of the TB's codeword.
+    c_init >= 0: the codeword is scrambled first (TS 38.211 6.3.1.1) with the device-generated sequence of c_init."""
     import torch
     C = msgs_bits.shape[0]
     d_cw, cstride, N = encode_messages(ctx, bg, Z, msgs_bits, None, stream)
@@ -115,6 +116,12 @@ def rate_matched_symbols(ctx: _lib.Context, bg: int, Z: int, msgs_bits: np.ndarr
     cc.rate_match_launch(ctx, specs, d_cw.data_ptr(), d_e.data_ptr(), stream)
     torch.cuda.synchronize()
     bits = torch.cat([_unpack(d_e[offs[i]:offs[i] + (E + 7) // 8], E) for i, E in enumerate(rm_lengths)])
+    if c_init >= 0:
+        from . import sequence_generators as sg
+        d_seq = torch.zeros((bits.numel() + 7) // 8, dtype=torch.uint8, device="cuda")
+        sg.scramble_bits_launch(ctx, [sg.prs_segment(bits.numel(), c_init)], 0, d_seq.data_ptr(), stream)
+        torch.cuda.synchronize()
+        bits = bits ^ _unpack(d_seq, bits.numel())
     z = modulate(bits, Qm)
     g = torch.Generator(device="cuda").manual_seed(seed)
     w = torch.complex(torch.randn(z.shape, device="cuda", generator=g), torch.randn(z.shape, device="cuda",
