@@ -824,6 +824,111 @@ struct dec {
     return RO.p == 1 && J < RO.npos && ext(RO.row, RO.e0[J]);
   }
 
+  /* ---- extension edges kept in registers (ldpc_spec.h, LDPC_SPEC_EXT_REG; int8 soft bits, one copy) ----
+   * State word X of a converted row, in the c2v slot its dropped pair left (srole: q0 + npos / 2): the low half is
+   * a = |v2c| of the extension edge (0..120, or >= 241 once infinite), the high half its sign g (0x0001 / 0xffff),
+   * which never changes. The v2c of a degree-1 column is the same at every visit until promotion_sum(c2v', v2c)
+   * overflows, and +-infinity with the same sign from then on, so no soft bit and no c2v are kept for the edge and
+   * nothing is written back: after the iterations nothing reads an extension column from LDS (the hard decision and
+   * the early-stop check read soft[0, K Z) only; grep s_soft).
+   * Every operation is a full-rate 32-bit or 16-bit VOP2 (tools/ubench/README.md): no compare / select. The 16-bit
+   * forms read the low halves of their sources and zero the high half of their result. */
+  /* 120 is a 32-bit literal of the instruction (2.6 against 2.1 cycles): the kernel has no SGPR to spare for it */
+  static __device__ __forceinline__ uint32_t min120_u16(uint32_t x)
+  {
+    uint32_t r;
+    asm("v_min_u16_e32 %0, 0x78, %1" : "=v"(r) : "v"(x));
+    return r;
+  }
+  static __device__ __forceinline__ uint32_t max_i16(uint32_t a, uint32_t b)
+  {
+    uint32_t r;
+    asm("v_max_i16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+  }
+  static __device__ __forceinline__ uint32_t add_u16(uint32_t a, uint32_t b)
+  {
+    uint32_t r;
+    asm("v_add_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+  }
+  static __device__ __forceinline__ uint32_t sub_u16(uint32_t a, uint32_t b) /* a - b */
+  {
+    uint32_t r;
+    asm("v_sub_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+  }
+  static __device__ __forceinline__ uint32_t sub120_u16(uint32_t b) /* 120 - b */
+  {
+    uint32_t r;
+    asm("v_sub_u16_e32 %0, 0x78, %1" : "=v"(r) : "v"(b));
+    return r;
+  }
+  static __device__ __forceinline__ uint32_t mul_u16(uint32_t a, uint32_t b)
+  {
+    uint32_t r;
+    asm("v_mul_lo_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+  }
+  static __device__ __forceinline__ uint32_t hi8_u16(uint32_t a) /* the low half's upper byte */
+  {
+    uint32_t r;
+    asm("v_lshrrev_b16_e32 %0, 8, %1" : "=v"(r) : "v"(a));
+    return r;
+  }
+
+  /* The state of an extension edge from its soft bit s (the prologue's LDS byte, +-121 = infinity): a = |s|, 241 for
+   * an infinite one; g = +1 for s >= 0 (the sign of d = s - 0 in pass1). */
+  static __device__ __forceinline__ uint32_t ext_state(int s)
+  {
+    const int      sv = s >> 31;
+    const uint32_t a  = static_cast<uint32_t>((s ^ sv) - sv);
+    return (a > static_cast<uint32_t>(LLR_MAX) ? 241U : a) | (static_cast<uint32_t>(sv | 1) << 16);
+  }
+  /* Before the first iteration (after the prologue's barrier): every converted row's state into its slot, from the
+   * extension column's byte at the lane's own check node. A lane belongs to one wave group and loads that group's. */
+  template <int S, int RI>
+  static __device__ __forceinline__ void ext_init_role(cr_t& cr, const lanes& L)
+  {
+    static constexpr spec::srole ro = G.steps[S].r[RI];
+    if constexpr (ro.row >= 0 && ro.xe >= 0) {
+      static_assert(ro.p == 1 && C1 && SB == 1 && (ro.npos & 1) == 0 && ro.q0 + ro.npos / 2 < NCR &&
+                        ext(ro.row, ro.xe) && ro.xcol == G.rows[ro.row].col[ro.xe],
+                    "extension edge in a register");
+      if (L.t1[ro.grp] < ZB) {
+        cr[ro.q0 + ro.npos / 2] = ext_state(rd8(L.t1[ro.grp], static_cast<uint32_t>(ro.xcol) * Z4));
+      }
+    }
+  }
+  template <int... Ss>
+  static __device__ __forceinline__ void ext_init(cr_t& cr, const lanes& L, std::integer_sequence<int, Ss...>)
+  {
+    ((ext_init_role<Ss, 0>(cr, L), ext_init_role<Ss, 1>(cr, L)), ...);
+  }
+  static __device__ __forceinline__ void ext_init(cr_t& cr, const lanes& L)
+  {
+    ext_init(cr, L, std::make_integer_sequence<int, G.n_steps>{});
+  }
+  /* The extension edge as the first edge of the two-minimum scan (start 120, strict <): M1.lo = min(a, 120), M2 stays
+   * at its start (an infinite edge moves neither), and the parity starts at g. */
+  static __device__ __forceinline__ void ext_seed(uint32_t X, u16x2& M1, u16x2& M2, uint32_t& SX)
+  {
+    M1 = as_u(min120_u16(X) | (static_cast<uint32_t>(LLR_MAX) << 16));
+    M2 = splatu(MIN_START);
+    SX = X >> 16;
+  }
+  /* The visit's update from the row's pass-2 constants (row_consts: n1, n2 + m1 and P = +-1, read from the low halves
+   * of the packed words, so no register beyond pass 2's): f = max(n1, n2 + m1 - a), u = a + P f, and a becomes
+   * infinite when u >= 121, i.e. when promotion_sum(c2v', v2c) overflows (pass2's note; an infinite a gives f = n1 and
+   * u >= 145, so it stays). The overflow ORs 255 into a, and a marker of 255 behaves like ext_state's 241 in every
+   * use: min(a, 120) = 120, n2 + m1 - a < 0 <= n1, u >= 145. */
+  static __device__ __forceinline__ void ext_update(uint32_t& X, s16x2 N1, s16x2 CC, s16x2 PP)
+  {
+    const uint32_t f = max_i16(bits(N1), sub_u16(bits(CC), X));
+    const uint32_t u = add_u16(X, mul_u16(f, bits(PP)));
+    X |= hi8_u16(sub120_u16(u)); /* 120 - u is in [-231, 216]: upper byte 0xff when negative, else 0 */
+  }
+
   /* A row's pass-1 state kept in registers across the step barrier (pipelined single-row chains, ldpc_spec.h):
    * addresses, signs and v2c magnitudes of the early pairs, and the partial minima and parity. */
   struct carry {
@@ -975,6 +1080,9 @@ struct dec {
     });
     u16x2    M1 = splatu(MIN_START), M2 = splatu(MIN_START);
     uint32_t SX = 0;
+    if constexpr (ro.xe >= 0) { /* the scan starts with the extension edge kept in a register */
+      ext_seed(cr[Q0 + NP], M1, M2, SX);
+    }
     static_for<NE>([&](auto ic) __attribute__((always_inline)) {
       constexpr int  i  = decltype(ic)::value;
       const uint32_t sx = __builtin_amdgcn_perm(static_cast<uint32_t>(hi[i]), static_cast<uint32_t>(lo[i]), 0x05040100U);
@@ -1005,6 +1113,9 @@ struct dec {
     int      lo[NP], hi[NP];
     u16x2    M1 = splatu(MIN_START), M2 = splatu(MIN_START);
     uint32_t SX = 0;
+    if constexpr (ro.xe >= 0 && NE == 0) { /* with early pairs, role_early seeded the scan */
+      ext_seed(cr[Q0 + NP], M1, M2, SX);
+    }
     if constexpr (NE > 0) {
       M1 = cy.m1;
       M2 = cy.m2;
@@ -1103,6 +1214,9 @@ struct dec {
         }
       }
     });
+    if constexpr (ro.xe >= 0) { /* no soft bit and no c2v for the extension edge: its sticky infinity only */
+      ext_update(cr[Q0 + NP], N1, CC, PP);
+    }
   }
 
   /* Wave priority (s_setprio) on graphs with W >= 3 waves per group: in a pipelined chain the group completing a row
@@ -2227,6 +2341,7 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
     typename SD::pf_t pf = {0, 0, 0, 0, 0};
     if constexpr (SPEC && !QUAD && !REG) {
       SD::template load_pf<0>(pf, sl);
+      SD::ext_init(cr, sl); /* the extension edges kept in registers: their state from the soft bits, once */
     }
     using RD = sp::rdec<SG::g, SG::r>;
     uint32_t rsv[REG ? SG::g.N_full : 1]; /* register-resident decoder: the columns' registers */

@@ -112,6 +112,24 @@ static_assert(SOFT_COPIES == 1 || SOFT_COPIES == 4, "soft-bit copies");
 constexpr int SOFT_BYTES = LDPC_SPEC_F16 ? 2 : 1;
 static_assert(SOFT_BYTES == 1 || SOFT_COPIES == 1, "binary16 soft bits: one copy per column");
 
+/* Extension edges in registers. Every row m >= 4 has one edge on its extension column (>= K + 4): degree 1, shift 0,
+ * read and written by this row's own lane only. For such a column the reference's messages are trivial: v2c at the
+ * next visit equals v2c at this visit unless promotion_sum(c2v', v2c) overflowed, and after an overflow it is
+ * +-infinity, with the sign of the original v2c, for the rest of the decode (tests/test_ext_edge_model.py checks both
+ * exhaustively against the oracle). So the edge needs no soft-bit read or write, no s - c, no c2v and no address: only
+ * its magnitude and sign in a register, and a sticky "went infinite" update per visit (dec::ext_update). Edges are
+ * processed in pairs and a row of odd degree carries a dummy half, so taking the extension edge out of an odd-degree
+ * row removes a whole pair (BG1: 26 of rows 4-45, 173 -> 147 pairs per check node and iteration); the state takes the
+ * c2v slot the pair leaves. Even-degree rows would lose no pair and keep their extension edge in LDS.
+ * ext_reg_graph gates the conversion per graph at compile time. */
+#ifndef LDPC_SPEC_EXT_REG
+#define LDPC_SPEC_EXT_REG 1
+#endif
+constexpr bool ext_reg_graph(int /* bg */, int /* W */)
+{
+  return LDPC_SPEC_EXT_REG != 0 && SOFT_BYTES == 1 && SOFT_COPIES == 1;
+}
+
 struct srow {
   int deg = 0;
   int e0  = 0; /* first edge of the row in row-major edge order */
@@ -122,9 +140,11 @@ struct srow {
 /* One role of a step: one row, its edge list per position. P = 1: e0[j]; P = 2: e0[j] (lanes 0-31) and e1[j]
  * (lanes 32-63), -1 = dummy. grp: the wave group that runs it (P = 1: waves [grp W, (grp + 1) W); P = 2: every wave).
  * nearly: positions [0, nearly) (whole pairs) were read and passed through pass 1 in the previous step by the same
- * wave group (see sstep::e). q0: first c2v pair slot (slots q0 .. q0 + (npos + 1) / 2 - 1 of the group's lanes). */
+ * wave group (see sstep::e). q0: first c2v pair slot (slots q0 .. q0 + (npos + 1) / 2 - 1 of the group's lanes).
+ * xe >= 0: the row's extension edge (column xcol) is not among the positions; its state is in slot q0 + npos / 2
+ * (LDPC_SPEC_EXT_REG; npos is even then). */
 struct srole {
-  int row = -1, p = 1, npos = 0, grp = 0, nearly = 0, q0 = 0;
+  int row = -1, p = 1, npos = 0, grp = 0, nearly = 0, q0 = 0, xe = -1, xcol = -1;
   int e0[MAX_POS] = {};
   int e1[MAX_POS] = {};
 };
@@ -178,12 +198,57 @@ constexpr bool row_has_column(const srow& r, int c)
 
 constexpr bool is_single_p1(const sstep& st) { return st.r[1].row < 0 && st.r[0].p == 1; }
 
+/* number of edges on column c in the whole graph */
+constexpr int column_degree(const sgraph& g, int c)
+{
+  int n = 0;
+  for (int m = 0; m < g.M; ++m) {
+    n += row_has_column(g.rows[m], c) ? 1 : 0;
+  }
+  return n;
+}
+
+/* every extension column (>= K + 4) has exactly one edge, with shift 0 */
+constexpr bool ext_columns_degree_one(const sgraph& g)
+{
+  for (int m = 0; m < g.M; ++m) {
+    for (int k = 0; k < g.rows[m].deg; ++k) {
+      const int c = g.rows[m].col[k];
+      if (c >= g.K + 4 && (g.rows[m].sh[k] != 0 || column_degree(g, c) != 1)) {
+        return false;
+      }
+    }
+  }
+  return true;
+}
+
+/* The edge of an unsplit role (p == 1) of row r that is kept in a register instead of a position (LDPC_SPEC_EXT_REG):
+ * the row's edge on a column >= K + 4 with shift 0, when that column has degree 1 in the whole graph and the row's
+ * degree is odd; -1 otherwise. */
+constexpr int ext_reg_edge(const sgraph& g, int r, int p)
+{
+  const srow& row = g.rows[r];
+  if (!ext_reg_graph(g.bg, g.W) || p != 1 || (row.deg & 1) == 0) {
+    return -1;
+  }
+  for (int k = 0; k < row.deg; ++k) {
+    if (row.col[k] >= g.K + 4 && row.sh[k] == 0 && column_degree(g, row.col[k]) == 1) {
+      return k;
+    }
+  }
+  return -1;
+}
+
 constexpr void make_role(const sgraph& g, srole& ro)
 {
   const int d = g.rows[ro.row].deg;
   if (ro.p == 1) {
+    ro.xe   = ext_reg_edge(g, ro.row, ro.p);
+    ro.xcol = ro.xe >= 0 ? g.rows[ro.row].col[ro.xe] : -1;
     for (int k = 0; k < d; ++k) {
-      ro.e0[ro.npos++] = k;
+      if (k != ro.xe) {
+        ro.e0[ro.npos++] = k;
+      }
     }
     return;
   }
@@ -259,14 +324,15 @@ constexpr sgraph make(int bg, int Z, int ils)
     int         ne   = 0;
     for (int pass = 0; pass < 2; ++pass) { /* non-shared edges first, then the shared ones */
       for (int k = 0; k < row.deg; ++k) {
-        if (row_has_column(prev, row.col[k]) == (pass == 1)) {
+        if (k != nx.xe && row_has_column(prev, row.col[k]) == (pass == 1)) {
           nx.e0[ne++] = k;
         }
       }
     }
+    ok = ok && ne == nx.npos;
     int early = 0;
     for (int k = 0; k < row.deg; ++k) {
-      early += row_has_column(prev, row.col[k]) ? 0 : 1;
+      early += (k == nx.xe || row_has_column(prev, row.col[k])) ? 0 : 1;
     }
     nx.nearly = early & ~1;
     if (nx.nearly > 0) {
@@ -281,7 +347,8 @@ constexpr sgraph make(int bg, int Z, int ils)
       if (ro.row < 0) {
         continue;
       }
-      const int np = (ro.npos + 1) / 2;
+      const int np = (ro.npos + 1) / 2 + (ro.xe >= 0 ? 1 : 0); /* the extension state: the slot of the pair it left */
+      ok           = ok && (ro.xe < 0 || (ro.npos & 1) == 0);
       if (ro.p == 2) {
         ro.q0  = cur[0] > cur[1] ? cur[0] : cur[1];
         cur[0] = cur[1] = ro.q0 + np;
@@ -312,7 +379,7 @@ constexpr bool early_roles_match(const sgraph& g)
     }
     const srole& c = g.steps[s + 1].r[0];
     if (c.row != e.row || c.grp != e.grp || c.q0 != e.q0 || c.nearly != e.nearly || c.npos != e.npos || c.p != 1 ||
-        e.grp == g.steps[s].r[0].grp || g.steps[s].r[1].row >= 0) {
+        c.xe != e.xe || c.xcol != e.xcol || e.grp == g.steps[s].r[0].grp || g.steps[s].r[1].row >= 0) {
       return false;
     }
     for (int j = 0; j < c.npos; ++j) {
@@ -350,7 +417,8 @@ constexpr bool schedule_is_layer_serial(const sgraph& g)
   return next == g.M;
 }
 
-/* Every edge of every row appears exactly once in its role's positions (per half for P = 2). */
+/* Every edge of every row appears exactly once in its role's positions (per half for P = 2), but for an extension edge
+ * kept in a register (srole::xe): that one is in none, and is the only edge of its degree-1, shift-0 column. */
 constexpr bool roles_cover_edges(const sgraph& g)
 {
   for (int s = 0; s < g.n_steps; ++s) {
@@ -365,9 +433,13 @@ constexpr bool roles_cover_edges(const sgraph& g)
           n += (ro.e0[j] == k) ? 1 : 0;
           n += (ro.p == 2 && ro.e1[j] == k) ? 1 : 0;
         }
-        if (n != 1) {
+        if (n != (k == ro.xe ? 0 : 1)) { /* the extension edge kept in a register is in no position */
           return false;
         }
+      }
+      if (ro.xe >= 0 && (ro.p != 1 || ro.xcol != g.rows[ro.row].col[ro.xe] || ro.xcol < g.K + 4 ||
+                         g.rows[ro.row].sh[ro.xe] != 0 || column_degree(g, ro.xcol) != 1 || (d & 1) == 0)) {
+        return false;
       }
     }
   }
@@ -601,7 +673,7 @@ constexpr int NOF_CORE_SPECS = 10; /* ids [0, 10): bodies of the mixed kernel */
 #define LDPC_SPEC_DEFINE(id, bg, z, ils)                                                                               \
   constexpr sgraph k_spec##id = make(bg, z, ils);                                                                      \
   static_assert(k_spec##id.valid && schedule_is_layer_serial(k_spec##id) && roles_cover_edges(k_spec##id) &&         \
-                    early_roles_match(k_spec##id),                                                                     \
+                    early_roles_match(k_spec##id) && ext_columns_degree_one(k_spec##id),                              \
                 "specialised schedule " #id);                                                                          \
   constexpr qgraph k_quad##id = make_quad(k_spec##id);                                                                 \
   static_assert(!is_quad(k_spec##id) || k_quad##id.valid, "lane-split schedule " #id);                              \
