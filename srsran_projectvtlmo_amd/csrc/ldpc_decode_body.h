@@ -197,38 +197,6 @@ __device__ __forceinline__ bool block_hard_decision(const int8_t* soft, uint8_t*
   return *reinterpret_cast<volatile uint32_t*>(s_flag) != token;
 }
 
-/* hard_decision of binary16 soft bits (the specialised decoders with ldpc_spec.h SOFT_BYTES = 2), same contract as
- * block_hard_decision: eight soft bits (16 bytes, one LDS read) per output byte. Per 16-bit half, t = (w & 0x7fff) +
- * 0x7fff has bit 15 set iff the magnitude is non-zero, so (w | ~t) & 0x8000 marks s <= 0 (sign set, or zero: the
- * decoder never forms -0, sp::pass2) and ~t & 0x8000 marks s == 0. gather2 puts a word's first soft bit (bit 15) above
- * its second (bit 31), MSB first. */
-__device__ __forceinline__ uint32_t gather2(uint32_t m) { return ((m >> 14) & 2U) | (m >> 31); }
-__device__ __forceinline__ bool block_hard_decision16(const int8_t* soft, uint8_t* hb, int KZ, uint32_t* s_flag,
-                                                      uint32_t token)
-{
-  const int nb   = (KZ + 7) / 8;
-  bool      zero = false;
-  for (int b = threadIdx.x; b < nb; b += blockDim.x) {
-    const uint4    w       = *reinterpret_cast<const uint4*>(soft + 16 * b);
-    const uint32_t keep    = 0xff00U >> min(8, KZ - 8 * b); /* valid bits of the last byte */
-    const uint32_t q[4]    = {w.x, w.y, w.z, w.w};
-    uint32_t       hard    = 0, zeros = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t t = (q[k] & 0x7fff7fffU) + 0x7fff7fffU;
-      hard |= gather2((q[k] | ~t) & 0x80008000U) << (6 - 2 * k);
-      zeros |= gather2(~t & 0x80008000U) << (6 - 2 * k);
-    }
-    zero  = zero || (zeros & keep) != 0;
-    hb[b] = static_cast<uint8_t>(hard & keep);
-  }
-  if (__builtin_amdgcn_ballot_w64(zero) != 0 && (threadIdx.x & 63) == 0) {
-    *reinterpret_cast<volatile uint32_t*>(s_flag) = token;
-  }
-  __syncthreads();
-  return *reinterpret_cast<volatile uint32_t*>(s_flag) != token;
-}
-
 /* Check-to-variable storage. c2v is kept per edge, as the reference keeps it (ldpc_decoder_impl.h:224-226), but
  * only for the edges that exist: int8 c2v[e][t] for graph edge e and lifted check node t (edge-major, stride Z, so
  * a wave's 64 consecutive check nodes read 64 consecutive bytes). BG1 Z=384: 316 * 384 = 121,344 B. An all-zero c2v
@@ -254,22 +222,6 @@ __device__ __forceinline__ int scale_mag(int m, float sf)
 }
 
 __device__ __forceinline__ int med3i(int x, int lo, int hi) { return min(max(x, lo), hi); } /* v_med3_i32 */
-
-/* binary16 soft bits of four clamped int8 LLRs (the specialised decoders' LDS, ldpc_spec.h SOFT_BYTES = 2):
- * x = b ^ 0x80 is b + 128 as an unsigned byte, so 0x6580 + x = 0x6600 + b is the binary16 pattern of 1536 + b (the
- * [1024, 2048) binade has unit spacing), and (1536 + b) - 1536 = b exactly, +0 for b = 0. Two v_perm, two v_add and
- * two packed subtractions per four LLRs. */
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint2 soft_f16x4(uint32_t w)
-{
-  const uint32_t x  = w ^ 0x80808080U;
-  const uint32_t lo = __builtin_amdgcn_perm(0U, x, 0x0c010c00U) + 0x65806580U;
-  const uint32_t hi = __builtin_amdgcn_perm(0U, x, 0x0c030c02U) + 0x65806580U;
-  const f16x2_t  k  = {static_cast<_Float16>(1536.0F), static_cast<_Float16>(1536.0F)};
-  return make_uint2(__builtin_bit_cast(uint32_t, __builtin_bit_cast(f16x2_t, lo) - k),
-                    __builtin_bit_cast(uint32_t, __builtin_bit_cast(f16x2_t, hi) - k));
-}
-__device__ __forceinline__ uint16_t soft_f16(int v) { return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v)); }
 
 /* Four int8 LLRs with +-127 (infinity) mapped to the decoder-internal +-121. */
 __device__ __forceinline__ uint32_t clamp_inf4(uint32_t w)
@@ -534,117 +486,28 @@ __device__ __forceinline__ u16x2 splatu(unsigned v)
 
 /* lane constants of the iteration */
 struct lanes {
-  uint32_t t1[2];   /* P = 1, wave group g: t = 64 * (wave - g W) + lane, and t + HI */
-  uint32_t t1h[2];
-  uint32_t t2, t2h; /* P = 2: t = 32 * wave + (lane & 31), and t + HI         */
-  uint32_t hmask;   /* P = 2: 0 for lanes 0-31, ~0 for lanes 32-63           */
+  uint32_t t1[2];   /* P = 1, wave group g: t = 64 * (wave - g W) + lane */
+  uint32_t t2;      /* P = 2: t = 32 * wave + (lane & 31)                 */
+  uint32_t hmask;   /* P = 2: 0 for lanes 0-31, ~0 for lanes 32-63        */
   int      wave, lane, nof_layers;
-  uint32_t one2;    /* SGPR constants (VOP2 with an SGPR source, not a 32-bit literal): int8 0x00010001 (pass1's
-                       v_or), binary16 the sign mask 0x80008000 */
-  uint32_t onef;    /* binary16: 1.0 in both halves (pass2) */
-  uint32_t sa[20];  /* split rows (P = 2, BG1 rows 0-3): the full LDS address of each position, two per word
-                       (16 bits each), computed once per decode (dec::fill_split) */
+  uint32_t one2;    /* 0x00010001 as an SGPR constant (pass1's v_or: VOP2 with an SGPR source, not a 32-bit literal) */
   uint32_t abase;   /* LDS byte address of this lane's first word of the split-address table (lay.c2v + 4 tid) */
   uint32_t act[3];  /* wave-uniform role masks (SGPRs): bit S of act[0] / act[1] / act[2] set when this wave runs the
                        step's first role / second role / the next row's early part (dec::role_masks) */
 };
 
-/* Soft bits (spec::SOFT_COPIES). One copy: column c at c * Z; edge k of check node t reads and writes
- * c * Z + (t + shift) mod Z, the modulo as min(t + shift, t + shift - Z) in unsigned arithmetic. Four copies: column c
- * at c * 4Z + {0, Z, 2Z, 3Z}; edge k reads p + Z with p = c * 4Z + t + shift (t + shift < 2Z, so p + Z is inside the
- * copies at Z and 2Z, no modulo) and writes p, p + Z and p + 2Z, which covers both read copies of index
- * (t + shift) mod Z whether or not t + shift wrapped. */
+/* Soft bits: int8 (ds_read_i8 / ds_write_b8), column c at c * Z; edge k of check node t reads and writes
+ * c * Z + (t + shift) mod Z, the modulo as min(t + shift, t + shift - Z) in unsigned arithmetic. */
 __device__ __forceinline__ int rd8(uint32_t base, uint32_t imm) { return *(lds_byte(base) + imm); }
 __device__ __forceinline__ void wr8(uint32_t base, uint32_t imm, uint32_t v)
 {
   *(lds_byte(base) + imm) = static_cast<int8_t>(v);
 }
-/* A soft bit of the specialised decoders (spec::SOFT_BYTES): int8 (ds_read_i8 / ds_write_b8) or binary16
- * (ds_read_u16 / ds_write_b16, its 16 bits in the low half); base + imm is a byte address. */
-typedef __attribute__((address_space(3))) uint16_t lds_u16;
-constexpr int SB = spec::SOFT_BYTES;
-__device__ __forceinline__ int rds(uint32_t base, uint32_t imm)
-{
-  if constexpr (SB == 2) {
-    return *reinterpret_cast<lds_u16*>(lds_byte(base) + imm);
-  } else {
-    return rd8(base, imm);
-  }
-}
-__device__ __forceinline__ void wrs(uint32_t base, uint32_t imm, uint32_t v)
-{
-  if constexpr (SB == 2) {
-    *reinterpret_cast<lds_u16*>(lds_byte(base) + imm) = static_cast<uint16_t>(v);
-  } else {
-    wr8(base, imm, v);
-  }
-}
-/* +infinity (the dummy position of an odd row, the scratch column): 121, or 121.0 in binary16 */
-constexpr int SOFT_INF = SB == 2 ? 0x5790 : 121;
+/* +infinity (the dummy position of an odd row, the scratch column) */
+constexpr int SOFT_INF = 121;
 /* the two-minimum scan's start: 120 (strict <: infinity and +-120 never change it) */
-constexpr unsigned MIN_START = SB == 2 ? 0x5780U : 120U;
+constexpr unsigned MIN_START = 120U;
 
-#if LDPC_SPEC_F16
-/* binary16 pairs. Every value is an integer of magnitude <= 337 (exact). min / max run on the bit patterns as 16-bit
- * integers: unsigned for magnitudes (non-negative), signed where one side may be negative (a negative binary16 is a
- * negative int16, and among non-negative values the integer order is the numeric one), so no float min/max (which
- * would canonicalise their inputs first). Constants: 120.0 = 0x5780, 121.0 = 0x5790, 1.0 = 0x3c00. */
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ h16x2 as_h(uint32_t x) { return __builtin_bit_cast(h16x2, x); }
-__device__ __forceinline__ uint32_t bits(h16x2 x) { return __builtin_bit_cast(uint32_t, x); }
-__device__ __forceinline__ h16x2 splath(float v) { return h16x2{static_cast<_Float16>(v), static_cast<_Float16>(v)}; }
-
-/* Pass 1 of an edge pair (binary16): d = s - c, its sign bits g (v_and), |d| (v_and), a = |v2c| with +infinity
- * marked by s^2 - 14400 = 241 (fma; <= 0 for a finite s), the per-half two-minimum and the sign parity (v_xor). */
-__device__ __forceinline__ void pass1(uint32_t S, uint32_t C, u16x2& M1, u16x2& M2, uint32_t& SX, uint32_t& G,
-                                      uint32_t& A, uint32_t smask)
-{
-  /* smask = 0x80008000 in an SGPR (VOP2 v_and with an SGPR source: no 32-bit literal, 2.1 cycles against 2.6) */
-  const h16x2    s  = as_h(S);
-  const uint32_t d  = bits(s - as_h(C));
-  uint32_t       g  = d & smask;
-  /* opaque: otherwise gfx950's v_bitop3_b32 (a half-rate VOP3) fuses g into |d| and into the parity XOR */
-  asm("" : "+v"(g));
-  const u16x2    af = __builtin_elementwise_min(as_u(d ^ g), splatu(0x5780U)); /* |d|: d without its sign bits */
-  const uint32_t iv = bits(__builtin_elementwise_fma(s, s, splath(-14400.0F)));
-  const u16x2    a  = as_u(bits(__builtin_elementwise_max(as_s(bits(af)), as_s(iv))));
-  M2                = __builtin_elementwise_min(M2, __builtin_elementwise_max(M1, a));
-  M1                = __builtin_elementwise_min(M1, a);
-  SX ^= g;
-  G = g;
-  A = bits(a);
-}
-
-/* Pass 2 (binary16), with the row's constants from row_consts: N1 = n1, CC = n2 + m1 and PP = the parity's sign
- * bit in both halves. f = max(n1, n2 + m1 - a) (see the int8 note below), P f by a sign flip (v_xor), soft' = sign(v2c)
- * min(a + P f, 121) as fma(u, +-1.0, +0) -- a plain product or sign flip would give -0 for u = 0, and a -0 soft bit
- * would count as negative in the next parity --, c2v' = sign(v2c) P f (v_xor). */
-__device__ __forceinline__ void pass2(uint32_t G, uint32_t A, s16x2 N1, s16x2 CC, s16x2 PP, uint32_t& Cnew,
-                                      uint32_t& Snew, uint32_t onef)
-{
-  /* onef = 1.0 in both halves (0x3c003c00) in an SGPR */
-  const h16x2    a  = as_h(A);
-  const s16x2    f  = __builtin_elementwise_max(N1, as_s(bits(as_h(bits(CC)) - a)));
-  const uint32_t pf = bits(f) ^ bits(PP);
-  const s16x2    u  = __builtin_elementwise_min(as_s(bits(a + as_h(pf))), splat(0x5790));
-  Snew              = bits(__builtin_elementwise_fma(as_h(bits(u)), as_h(G | onef), splath(0.0F)));
-  Cnew              = pf ^ G;
-}
-
-/* The row's pass-2 constants from its two minima (binary16 bit patterns) and parity word: round(0.8 m) =
- * fma(m, 0.8, 1024) - 1024 (one rounding to the integer grid of [1024, 2048); 0.8 in binary16 is 0.7998, off by
- * < 0.024 for m <= 120, while 0.8 m is never within 0.1 of a half: exact), both minima in one packed fma. */
-__device__ __forceinline__ void row_consts(uint32_t m1, uint32_t m2, uint32_t sx, s16x2& N1, s16x2& CC, s16x2& PP)
-{
-  const h16x2 nn = __builtin_elementwise_fma(as_h(m1 | (m2 << 16)), splath(0.7998046875F), splath(1024.0F)) -
-                   splath(1024.0F);
-  const s16x2 t  = as_s(bits(nn + as_h(m1 << 16))); /* (n1, n2 + m1) */
-  /* swizzled splats: the packed consumers read them through op_sel, no splat instruction */
-  N1 = t.xx;
-  CC = t.yy;
-  PP = splat(static_cast<short>(sx & 0x8000U));
-}
-#else
 /* Pass 1 of an edge pair: v2c = soft (-) c2v per half, its magnitude a (+infinity -> 241) and the per-half
  * two-minimum and parity updates. Arithmetic note at pass2. */
 __device__ __forceinline__ void pass1(uint32_t S, uint32_t C, u16x2& M1, u16x2& M2, uint32_t& SX, uint32_t& G,
@@ -679,9 +542,8 @@ __device__ __forceinline__ void pass1(uint32_t S, uint32_t C, u16x2& M1, u16x2& 
  *   soft' = promotion_sum(c2v', v2c) = sign(v2c) * min(a + P f, 121): a + P f >= -96, and an infinite v2c (a = 241)
  *           stays at 121. */
 __device__ __forceinline__ void pass2(uint32_t G, uint32_t A, s16x2 N1, s16x2 CC, s16x2 PP, uint32_t& Cnew,
-                                      uint32_t& Snew, uint32_t onef)
+                                      uint32_t& Snew)
 {
-  (void)onef;
   const s16x2 a  = as_s(A);
   const s16x2 g  = as_s(G);
   const s16x2 f  = __builtin_elementwise_max(N1, CC - a);
@@ -701,7 +563,6 @@ __device__ __forceinline__ void row_consts(uint32_t m1, uint32_t m2, uint32_t sx
   CC                = splat(static_cast<int>(n2 + m1));
   PP                = splat(static_cast<short>(sx | 1U));
 }
-#endif
 
 /* The check node's two minima and parity from the per-half ones: min1 = min(A, B), min2 = min(min2_A, min2_B,
  * max(min1_A, min1_B)) -- the two smallest of the multiset, as the sequential scan finds them. Parity: each half of SX
@@ -729,49 +590,35 @@ __device__ __forceinline__ void merge_partner(uint32_t& m1, uint32_t& m2, uint32
 
 template <const spec::sgraph& G>
 struct dec {
-  static constexpr int      Z       = G.Z;
-  static constexpr bool     C1      = spec::SOFT_COPIES == 1; /* one copy: the lane wraps t + shift itself */
-  static constexpr uint32_t ZB      = static_cast<uint32_t>(SB) * G.Z; /* bytes per Z soft bits */
-  static constexpr uint32_t Z4      = static_cast<uint32_t>(spec::SOFT_COPIES) * ZB; /* column stride (bytes) */
+  static constexpr uint32_t Z       = static_cast<uint32_t>(G.Z); /* column stride: one int8 soft bit per byte */
   static constexpr int      NCR     = G.slots;
-  static constexpr int      KC      = G.K + 4;                              /* first extension column */
-  static constexpr uint32_t SCRATCH = static_cast<uint32_t>(G.N_full) * Z4; /* dummy edges: soft +infinity */
-  static constexpr uint32_t HI      = 49152U; /* second address base: every ds immediate fits 16 bits */
-  static constexpr int      P2_WAVES = (Z + 31) / 32;
+  static constexpr int      KC      = G.K + 4;                             /* first extension column */
+  static constexpr uint32_t SCRATCH = static_cast<uint32_t>(G.N_full) * Z; /* dummy edges: soft +infinity */
+  static constexpr int      P2_WAVES = (G.Z + 31) / 32;
   static_assert(G.valid && 2 * G.W <= 12 && P2_WAVES <= 12, "specialised schedule");
 
   using cr_t = uint32_t[NCR];
 
-  /* byte offset of edge e of row r in its column's copy at offset 0 (col * 4Z + shift); a dummy edge (e < 0) uses the
+  /* byte offset of the column of edge e of row r (the ds immediate of its accesses); a dummy edge (e < 0) uses the
    * scratch column */
   static constexpr uint32_t off(int r, int e)
   {
-    return e < 0 ? SCRATCH : static_cast<uint32_t>(G.rows[r].col[e]) * Z4 + (C1 ? 0U : shift(r, e));
+    return e < 0 ? SCRATCH : static_cast<uint32_t>(G.rows[r].col[e]) * Z;
   }
   static constexpr uint32_t shift(int r, int e) { return e < 0 ? 0U : static_cast<uint32_t>(G.rows[r].sh[e]); }
-  static constexpr uint32_t shb(int r, int e) { return static_cast<uint32_t>(SB) * shift(r, e); } /* in bytes */
-  /* read/write offset of the copy the decoder uses, relative to off() */
-  static constexpr uint32_t RD = C1 ? 0U : static_cast<uint32_t>(G.Z);
-  /* extension edge: a degree-1 column (>= K + 4) with shift 0, read and written by this row only -> one copy */
+  /* extension edge: a degree-1 column (>= K + 4) with shift 0, read and written by this row only */
   static constexpr bool     ext(int r, int e) { return e >= 0 && G.rows[r].col[e] >= KC && G.rows[r].sh[e] == 0; }
-  static constexpr bool     hi_base(uint32_t o) { return !C1 && o + 3U * Z > 65535U; }
-  static_assert(!C1 || SCRATCH + ZB <= 65535U, "one-copy layout: column offsets are ds immediates");
+  static_assert(SCRATCH + Z <= 65535U, "column offsets are ds immediates");
 
-
-  /* one copy: (t + sh) mod Z = min(t + sh, t + sh - Z) as unsigned (t < Z, sh < Z) */
-#if defined(LDPC_SPEC_WRAP32)
-  static __device__ __forceinline__ uint32_t wrap(uint32_t x) { return __builtin_elementwise_min(x, x - ZB); }
-#else
-  /* v_min_u32 is a half-rate instruction; the 16-bit VOP2 v_min_u16 issues at full rate and zeroes the upper half of
-   * its result (tools/ubench/README.md), and x, x - Z mod 2^16 order the same way as in 32 bits (x < 2Z <= 2^16) */
+  /* (t + sh) mod Z = min(t + sh, t + sh - Z) as unsigned (t < Z, sh < Z). v_min_u32 is a half-rate instruction; the
+   * 16-bit VOP2 v_min_u16 issues at full rate and zeroes the upper half of its result (tools/ubench/README.md), and
+   * x, x - Z mod 2^16 order the same way as in 32 bits (x < 2Z <= 2^16) */
   static __device__ __forceinline__ uint32_t wrap(uint32_t x)
   {
     uint32_t r;
-    asm("v_min_u16_e32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(x - ZB));
+    asm("v_min_u16_e32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(x - Z));
     return r;
   }
-#endif
-  static constexpr uint32_t imm(uint32_t o) { return hi_base(o) ? o - HI : o; }
 
   template <int P, int GRP>
   static __device__ __forceinline__ bool lane_active(const lanes& L)
@@ -779,9 +626,9 @@ struct dec {
     if constexpr (Z % 64 == 0) {
       return true;
     } else if constexpr (P == 2) {
-      return L.t2 < ZB;
+      return L.t2 < Z;
     } else {
-      return L.t1[GRP] < ZB;
+      return L.t1[GRP] < Z;
     }
   }
 
@@ -789,42 +636,28 @@ struct dec {
   template <const spec::srole& RO, int J>
   static __device__ __forceinline__ uint32_t pos_base(const lanes& L)
   {
-    if constexpr (C1) {
-      constexpr int e0 = J < RO.npos ? RO.e0[J] : -1;
-      if constexpr (RO.p == 1) {
-        constexpr uint32_t sh = shb(RO.row, e0);
-        return sh == 0 ? L.t1[RO.grp] : wrap(L.t1[RO.grp] + sh);
-      } else {
-        constexpr int      e1  = J < RO.npos ? RO.e1[J] : -1;
-        constexpr uint32_t sh0 = shb(RO.row, e0), sh1 = shb(RO.row, e1);
-        uint32_t           x   = L.t2;
-        if constexpr (sh0 != 0 || sh1 != 0) {
-          x = wrap(x + sh0 + (sh1 != sh0 ? (L.hmask & (sh1 - sh0)) : 0U));
-        }
-        constexpr uint32_t o0 = off(RO.row, e0), o1 = off(RO.row, e1);
-        return o1 == o0 ? x : x + (L.hmask & (o1 - o0)); /* upper half: its own column */
-      }
-    } else if constexpr (RO.p == 1) {
-      constexpr uint32_t o = off(RO.row, J < RO.npos ? RO.e0[J] : -1);
-      return hi_base(o) ? L.t1h[RO.grp] : L.t1[RO.grp];
+    constexpr int e0 = J < RO.npos ? RO.e0[J] : -1;
+    if constexpr (RO.p == 1) {
+      constexpr uint32_t sh = shift(RO.row, e0);
+      return sh == 0 ? L.t1[RO.grp] : wrap(L.t1[RO.grp] + sh);
     } else {
-      constexpr uint32_t o0 = off(RO.row, J < RO.npos ? RO.e0[J] : -1);
-      constexpr uint32_t o1 = off(RO.row, J < RO.npos ? RO.e1[J] : -1);
-      return (hi_base(o0) ? L.t2h : L.t2) + (L.hmask & (o1 - o0)); /* upper half: its own edge's offset */
+      constexpr int      e1  = J < RO.npos ? RO.e1[J] : -1;
+      constexpr uint32_t sh0 = shift(RO.row, e0), sh1 = shift(RO.row, e1);
+      uint32_t           x   = L.t2;
+      if constexpr (sh0 != 0 || sh1 != 0) {
+        x = wrap(x + sh0 + (sh1 != sh0 ? (L.hmask & (sh1 - sh0)) : 0U));
+      }
+      constexpr uint32_t o0 = off(RO.row, e0), o1 = off(RO.row, e1);
+      return o1 == o0 ? x : x + (L.hmask & (o1 - o0)); /* upper half: its own column */
     }
   }
   template <const spec::srole& RO, int J>
   static constexpr uint32_t pos_imm()
   {
-    return imm(off(RO.row, J < RO.npos ? RO.e0[J] : -1));
-  }
-  template <const spec::srole& RO, int J>
-  static constexpr bool pos_ext()
-  {
-    return RO.p == 1 && J < RO.npos && ext(RO.row, RO.e0[J]);
+    return off(RO.row, J < RO.npos ? RO.e0[J] : -1);
   }
 
-  /* ---- extension edges kept in registers (ldpc_spec.h, LDPC_SPEC_EXT_REG; int8 soft bits, one copy) ----
+  /* ---- extension edges kept in registers (ldpc_spec.h, ext_reg_edge) ----
    * State word X of a converted row, in the c2v slot its dropped pair left (srole: q0 + npos / 2): the low half is
    * a = |v2c| of the extension edge (0..120, or >= 241 once infinite), the high half its sign g (0x0001 / 0xffff),
    * which never changes. The v2c of a degree-1 column is the same at every visit until promotion_sum(c2v', v2c)
@@ -892,11 +725,11 @@ struct dec {
   {
     static constexpr spec::srole ro = G.steps[S].r[RI];
     if constexpr (ro.row >= 0 && ro.xe >= 0) {
-      static_assert(ro.p == 1 && C1 && SB == 1 && (ro.npos & 1) == 0 && ro.q0 + ro.npos / 2 < NCR &&
+      static_assert(ro.p == 1 && (ro.npos & 1) == 0 && ro.q0 + ro.npos / 2 < NCR &&
                         ext(ro.row, ro.xe) && ro.xcol == G.rows[ro.row].col[ro.xe],
                     "extension edge in a register");
-      if (L.t1[ro.grp] < ZB) {
-        cr[ro.q0 + ro.npos / 2] = ext_state(rd8(L.t1[ro.grp], static_cast<uint32_t>(ro.xcol) * Z4));
+      if (L.t1[ro.grp] < Z) {
+        cr[ro.q0 + ro.npos / 2] = ext_state(rd8(L.t1[ro.grp], static_cast<uint32_t>(ro.xcol) * Z));
       }
     }
   }
@@ -940,81 +773,38 @@ struct dec {
 
   /* Split rows (P = 2): the upper half's column and shift differ from the lower half's at every position, so an
    * address costs 6-7 VALU ops (per-half deltas, wrap, column) against 3 on an unsplit row. BG1's four split rows have
-   * 40 positions per lane whose addresses never change during a decode: they can be computed once (fill_split) and
-   * kept as 16-bit halves of registers (every LDS address is below 64 KiB), a position then costing one unpack op. */
-#ifndef LDPC_SPEC_SPLIT_ADDR
-#define LDPC_SPEC_SPLIT_ADDR 1
-#endif
-/* Round 2 kept rows 0-1's pairs in 20 registers (the Z=384 kernel was at 168 VGPRs with 8 B/lane of spills; rows 0-1
- * against none: 149.1 -> 147.8 us, profiles/r02/split_addr.txt). Round 3 moved all four rows' pairs to the LDS table
- * below (152 VGPRs, no spill), which is what lets the kernel carry a second iteration loop (iteration_partial) without
- * spilling; the table words are read a step ahead (load_pf), so C2 is unchanged within 0.5%
- * (profiles/r03/partial_ab.txt). */
-/* Split rows [LDPC_SPEC_SPLIT_ADDR_ROWS, LDPC_SPEC_SPLIT_LDS_ROWS) keep their precomputed address pairs in LDS instead
- * (one 32-bit word per pair and lane, lane-contiguous: one conflict-free ds_read_b32 and two full-rate unpack ops per
- * pair, against 6-7 VALU ops per position computed in the step, and no registers held across the iteration). The
- * table sits in the specialised layout's c2v region (lay.c2v, unused there: c2v lives in registers); make_lds_layout
- * reserves it (spec::SPLIT_LDS_PAIRS). Each lane writes and reads only its own words, so it needs no barrier. Only BG1
- * graphs have the tables (write_split_tables); split rows of BG2 graphs compute their addresses in the step. */
+   * 40 positions per lane whose addresses never change during a decode: they are computed once per context
+   * (write_split_table) and kept as 16-bit halves of words (every LDS address is below 64 KiB).
+   * Round 2 kept rows 0-1's pairs in 20 registers (the Z=384 kernel was at 168 VGPRs with 8 B/lane of spills; rows 0-1
+   * against none: 149.1 -> 147.8 us, profiles/r02/split_addr.txt). Round 3 moved all four rows' pairs to the LDS table
+   * below (152 VGPRs, no spill), which is what lets the kernel carry a second iteration loop (iteration_partial)
+   * without spilling; the table words are read a step ahead (load_pf), so C2 is unchanged within 0.5%
+   * (profiles/r03/partial_ab.txt).
+   * Split rows [0, LDPC_SPEC_SPLIT_LDS_ROWS) keep their precomputed address pairs in LDS (one 32-bit word per pair and
+   * lane, lane-contiguous: one conflict-free ds_read_b32 and two full-rate unpack ops per pair, against 6-7 VALU ops
+   * per position computed in the step, and no registers held across the iteration). The table sits in the specialised
+   * layout's c2v region (lay.c2v, unused there: c2v lives in registers); make_lds_layout reserves it
+   * (spec::SPLIT_LDS_PAIRS). The prologue copies it from the context's global copy. Only BG1 graphs have the tables
+   * (write_split_tables); split rows of BG2 graphs compute their addresses in the step. */
   static constexpr uint32_t WG = static_cast<uint32_t>(G.waves) * 64U; /* table stride: lanes per workgroup */
-  template <bool LDS>
-  static constexpr int split_pairs_before_t(int S)
+  static constexpr int lds_pairs_before(int S)
   {
     int n = 0;
     for (int s = 0; s < S; ++s) {
-      const spec::srole& r  = G.steps[s].r[0];
-      const bool         in = LDS ? (r.row >= LDPC_SPEC_SPLIT_ADDR_ROWS && r.row < LDPC_SPEC_SPLIT_LDS_ROWS)
-                                  : r.row < LDPC_SPEC_SPLIT_ADDR_ROWS;
-      n += (G.bg == 1 && r.p == 2 && in) ? (r.npos + 1) / 2 : 0;
+      const spec::srole& r = G.steps[s].r[0];
+      n += (G.bg == 1 && r.p == 2 && r.row < LDPC_SPEC_SPLIT_LDS_ROWS) ? (r.npos + 1) / 2 : 0;
     }
     return n;
   }
-  static constexpr int split_pairs_before(int S) { return split_pairs_before_t<false>(S); }
-  static constexpr int lds_pairs_before(int S) { return split_pairs_before_t<true>(S); }
-  static_assert(split_pairs_before(G.n_steps) <= 20, "lanes::sa holds the split rows' address pairs");
   static_assert(lds_pairs_before(G.n_steps) <= spec::SPLIT_LDS_PAIRS, "make_lds_layout reserves the table");
   static_assert(static_cast<uint32_t>(spec::SPLIT_LDS_PAIRS) * WG * 4U <= 65536U, "table offsets are ds immediates");
   template <const spec::srole& RO>
-  static constexpr bool pre_addr()
-  {
-    return LDPC_SPEC_SPLIT_ADDR && C1 && G.bg == 1 && RO.p == 2 && RO.row < LDPC_SPEC_SPLIT_ADDR_ROWS;
-  }
-  template <const spec::srole& RO>
   static constexpr bool pre_lds()
   {
-    return LDPC_SPEC_SPLIT_ADDR && C1 && G.bg == 1 && RO.p == 2 && RO.row >= LDPC_SPEC_SPLIT_ADDR_ROWS &&
-           RO.row < LDPC_SPEC_SPLIT_LDS_ROWS;
+    return G.bg == 1 && RO.p == 2 && RO.row < LDPC_SPEC_SPLIT_LDS_ROWS;
   }
   static_assert(lds_pairs_before(G.n_steps) * static_cast<int>(WG) <= SPLIT_TAB_STRIDE, "global split-table stride");
   static constexpr int LDS_PAIRS = lds_pairs_before(G.n_steps);
-  template <int S>
-  static __device__ __forceinline__ void fill_split_step(lanes& L, uint32_t* __restrict__ gdst)
-  {
-    static constexpr spec::srole ro = G.steps[S].r[0];
-    if constexpr (pre_addr<ro>() || pre_lds<ro>()) {
-      constexpr int K0 = pre_addr<ro>() ? split_pairs_before(S) : lds_pairs_before(S);
-      static_for<(ro.npos + 1) / 2>([&](auto ic) __attribute__((always_inline)) {
-        constexpr int  i  = decltype(ic)::value;
-        const uint32_t lo = pos_base<ro, 2 * i>(L) + pos_imm<ro, 2 * i>();
-        const uint32_t hi = (2 * i + 1 < ro.npos) ? pos_base<ro, 2 * i + 1>(L) + pos_imm<ro, 2 * i + 1>() : 0U;
-        const uint32_t w  = (lo & 0xffffU) | (hi << 16);
-        if constexpr (pre_addr<ro>()) {
-          L.sa[K0 + i] = w;
-        } else if (L.wave < P2_WAVES) {
-          if (gdst != nullptr) { /* the context's global copy (write_split_table) */
-            gdst[static_cast<uint32_t>(K0 + i) * WG + static_cast<uint32_t>(L.wave * 64 + L.lane)] = w;
-          } else {
-            *lds_word(L.abase + static_cast<uint32_t>(K0 + i) * WG * 4U) = w;
-          }
-        }
-      });
-    }
-  }
-  template <int... Ss>
-  static __device__ __forceinline__ void fill_split(lanes& L, std::integer_sequence<int, Ss...>, uint32_t* gdst = nullptr)
-  {
-    (fill_split_step<Ss>(L, gdst), ...);
-  }
 
   /* The LDS-table words of a split step's address pairs, read one step ahead (at the start of the previous step,
    * whose barrier then covers their latency; step 0's at the end of the previous iteration or before the loop). */
@@ -1044,9 +834,8 @@ struct dec {
     if constexpr (RO.p == 2) {
       /* the upper half's per-position address deltas are iteration-invariant: computed here, not hoisted */
       L.t2    = opaque(L0.t2);
-      L.t2h   = opaque(L0.t2h);
       L.hmask = opaque(L0.hmask);
-    } else if constexpr (C1) {
+    } else {
       L.t1[RO.grp] = opaque(L0.t1[RO.grp]);
     }
     return L;
@@ -1069,8 +858,8 @@ struct dec {
       constexpr int i = decltype(ic)::value;
       cy.base[2 * i]     = pos_base<ro, 2 * i>(L);
       cy.base[2 * i + 1] = pos_base<ro, 2 * i + 1>(L);
-      lo[i]              = rds(cy.base[2 * i], pos_imm<ro, 2 * i>() + RD);
-      hi[i]              = rds(cy.base[2 * i + 1], pos_imm<ro, 2 * i + 1>() + RD);
+      lo[i]              = rd8(cy.base[2 * i], pos_imm<ro, 2 * i>());
+      hi[i]              = rd8(cy.base[2 * i + 1], pos_imm<ro, 2 * i + 1>());
     });
     /* the late positions' addresses too (no data dependency): off the completing waves' path in the next step */
     static_for<NP - NE>([&](auto ic) __attribute__((always_inline)) {
@@ -1102,9 +891,7 @@ struct dec {
     constexpr int                Q0 = ro.q0;
     constexpr int                NP = (ro.npos + 1) / 2; /* pairs */
     constexpr int                NE = ro.nearly / 2;     /* pairs run early */
-    constexpr bool               PRE = pre_addr<ro>() || pre_lds<ro>(); /* split row: addresses precomputed */
-    constexpr bool               PRL = pre_lds<ro>();                    /* ... and kept in LDS              */
-    constexpr int                SK  = PRL ? lds_pairs_before(S) : split_pairs_before(S);
+    constexpr bool               PRE = pre_lds<ro>(); /* split row: addresses precomputed, in the LDS table */
     const lanes                  L  = role_lanes<ro>(L0);
     if (!lane_active<ro.p, ro.grp>(L)) {
       return;
@@ -1133,21 +920,17 @@ struct dec {
       if constexpr (NE > 0) { /* computed by the early role */
         base[2 * i]     = cy.base[2 * i];
         base[2 * i + 1] = cy.base[2 * i + 1];
-      } else
-      if constexpr (PRL) { /* full addresses from the LDS table (fill_split), read ahead (load_pf); immediate 0 */
+      } else if constexpr (PRE) { /* full addresses from the LDS table, read ahead (load_pf); immediate 0 */
         const uint32_t w = pf[i];
         base[2 * i]      = w & 0xffffU;
         base[2 * i + 1]  = w >> 16;
-      } else if constexpr (PRE) { /* full addresses, precomputed (fill_split); immediate 0 */
-        base[2 * i]     = L.sa[SK + i] & 0xffffU;
-        base[2 * i + 1] = L.sa[SK + i] >> 16;
       } else {
         base[2 * i]     = pos_base<ro, 2 * i>(L);
         base[2 * i + 1] = pos_base<ro, 2 * i + 1>(L);
       }
-      lo[i]           = rds(base[2 * i], (PRE ? 0U : pos_imm<ro, 2 * i>()) + RD);
+      lo[i]           = rd8(base[2 * i], PRE ? 0U : pos_imm<ro, 2 * i>());
       /* a position past the role's last (both halves dummy): +infinity without a read */
-      hi[i] = (2 * i + 1 < ro.npos) ? rds(base[2 * i + 1], (PRE ? 0U : pos_imm<ro, 2 * i + 1>()) + RD) : SOFT_INF;
+      hi[i] = (2 * i + 1 < ro.npos) ? rd8(base[2 * i + 1], PRE ? 0U : pos_imm<ro, 2 * i + 1>()) : SOFT_INF;
     });
     static_for<NP - NE>([&](auto ic) __attribute__((always_inline)) {
       constexpr int i = NE + decltype(ic)::value;
@@ -1176,7 +959,7 @@ struct dec {
     if constexpr (P2B) {
       static_for<NP>([&](auto ic) __attribute__((always_inline)) {
         constexpr int i = decltype(ic)::value;
-        pass2(Gs[i], A[i], N1, CC, PP, cr[Q0 + i], snv[i], L.onef);
+        pass2(Gs[i], A[i], N1, CC, PP, cr[Q0 + i], snv[i]);
       });
     }
     static_for<NP>([&](auto ic) __attribute__((always_inline)) {
@@ -1185,33 +968,12 @@ struct dec {
       if constexpr (P2B) {
         sn = snv[i];
       } else {
-        pass2(Gs[i], A[i], N1, CC, PP, cr[Q0 + i], sn, L.onef);
+        pass2(Gs[i], A[i], N1, CC, PP, cr[Q0 + i], sn);
       }
       constexpr uint32_t i0 = PRE ? 0U : pos_imm<ro, 2 * i>(), i1 = PRE ? 0U : pos_imm<ro, 2 * i + 1>();
-      if constexpr (pos_ext<ro, 2 * i>()) {
-        wrs(base[2 * i], i0 + RD, sn); /* t + 0 never wraps and only this row reads it: one copy */
-      } else {
-        if constexpr (C1) {
-          wrs(base[2 * i], i0, sn);
-        } else {
-          wrs(base[2 * i], i0, sn);
-          wrs(base[2 * i], i0 + Z, sn);
-          wrs(base[2 * i], i0 + 2 * Z, sn);
-        }
-      }
-      const uint32_t sh = sn >> 16;
-      if constexpr (2 * i + 1 >= ro.npos) {
-        /* dummy: nothing to write */
-      } else if constexpr (pos_ext<ro, 2 * i + 1>()) {
-        wrs(base[2 * i + 1], i1 + RD, sh);
-      } else {
-        if constexpr (C1) {
-          wrs(base[2 * i + 1], i1, sh);
-        } else {
-          wrs(base[2 * i + 1], i1, sh);
-          wrs(base[2 * i + 1], i1 + Z, sh);
-          wrs(base[2 * i + 1], i1 + 2 * Z, sh);
-        }
+      wr8(base[2 * i], i0, sn);
+      if constexpr (2 * i + 1 < ro.npos) { /* else a dummy: nothing to write */
+        wr8(base[2 * i + 1], i1, sn >> 16);
       }
     });
     if constexpr (ro.xe >= 0) { /* no soft bit and no c2v for the extension edge: its sticky infinity only */
@@ -1224,13 +986,11 @@ struct dec {
    * completing waves first when both compete for a SIMD. C2 batch 150.4 -> 148.9 us, BG1 Z = 256 119.2 -> 116.8 us;
    * on BG2 Z = 128 (W = 2) it was 1% slower, so the smaller graphs keep equal priorities
    * (profiles/r02/prio.txt). */
-#ifndef LDPC_SPEC_WAVE_PRIO
-#define LDPC_SPEC_WAVE_PRIO 1
-#endif
+  static constexpr bool WAVE_PRIO = true;
   template <int PR>
   static __device__ __forceinline__ void set_prio()
   {
-    if constexpr (LDPC_SPEC_WAVE_PRIO && G.W >= 3) {
+    if constexpr (WAVE_PRIO && G.W >= 3) {
       __builtin_amdgcn_s_setprio(PR);
     }
   }
@@ -1293,9 +1053,6 @@ struct dec {
     iteration_impl(cr, L, pf, std::make_integer_sequence<int, G.n_steps>{});
   }
 
-#ifndef LDPC_SPEC_PARTIAL_LAYERS
-#define LDPC_SPEC_PARTIAL_LAYERS 12
-#endif
   /* Codeblocks with few layers (high code rate: impl.cpp:103-114 adapts the layer count to the codeblock length, a
    * 6-layer BG1 Z=384 CB in C4's large TB). Steps run in row order, so once a step's first row is beyond the layer
    * count every later step is empty too; an empty step still costs every wave its scalar role checks (about 20 SALU
@@ -1303,7 +1060,7 @@ struct dec {
    * them in its 28 empty steps). Codeblocks with at most PARTIAL_LAYERS layers run this iteration instead: the first
    * PARTIAL_STEPS steps, ending at the first empty one. Full-length codeblocks keep the unchecked iteration (the
    * checks in every step cost C2 1-2%, profiles/r03/exit_ab.txt). */
-  static constexpr int PARTIAL_LAYERS = LDPC_SPEC_PARTIAL_LAYERS;
+  static constexpr int PARTIAL_LAYERS = 12;
   static constexpr int partial_steps()
   {
     int n = 0;
@@ -1396,7 +1153,6 @@ struct dec {
     L.act[2] = opaque_s(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(ae))));
   }
 
-  template <bool FILL>
   static __device__ __forceinline__ lanes make_lanes(int wave, int lane, int nof_layers, uint32_t abase)
   {
     lanes L{};
@@ -1404,32 +1160,43 @@ struct dec {
     L.wave       = wave;
     L.lane       = lane;
     L.nof_layers = nof_layers;
-    L.one2       = opaque_s(SB == 2 ? 0x80008000U : 0x00010001U);
-    L.onef       = opaque_s(0x3c003c00U);
+    L.one2       = opaque_s(0x00010001U);
     for (int i = 0; i < 2; ++i) { /* byte offsets of the lane's check node */
-      L.t1[i]  = static_cast<uint32_t>(SB * ((wave - i * G.W) * 64 + lane));
-      L.t1h[i] = L.t1[i] + HI;
+      L.t1[i] = static_cast<uint32_t>((wave - i * G.W) * 64 + lane);
     }
-    L.t2    = static_cast<uint32_t>(SB * (wave * 32 + (lane & 31)));
-    L.t2h   = L.t2 + HI;
+    L.t2    = static_cast<uint32_t>(wave * 32 + (lane & 31));
     L.hmask = (lane >= 32) ? 0xffffffffU : 0U;
-    for (auto& w : L.sa) {
-      w = 0;
-    }
-    if constexpr (FILL && !LDPC_SPEC_SPLIT_COPY) {
-      fill_split(L, std::make_integer_sequence<int, G.n_steps>{});
-    }
     role_masks(L);
     return L;
   }
 
-  /* The split-row address table of this graph into global memory (ldpc_split_table_kernel, once per context): the
-   * words fill_split would write into LDS, at the same word index, so a codeblock's prologue copies them instead of
-   * computing them (about 300 VALU instructions per lane, 1.1 us per codeblock at Z = 384). */
+  /* The split-row address table of this graph into global memory (ldpc_split_table_kernel, once per context): word
+   * (pair index) * WG + tid holds the full LDS addresses of the lane's positions 2 i and 2 i + 1 of a split row, so a
+   * codeblock's prologue copies them instead of computing them (about 300 VALU instructions per lane, 1.1 us per
+   * codeblock at Z = 384). */
+  template <int S>
+  static __device__ __forceinline__ void write_split_step(uint32_t* __restrict__ gdst, const lanes& L)
+  {
+    static constexpr spec::srole ro = G.steps[S].r[0];
+    if constexpr (pre_lds<ro>()) {
+      constexpr int K0 = lds_pairs_before(S);
+      static_for<(ro.npos + 1) / 2>([&](auto ic) __attribute__((always_inline)) {
+        constexpr int  i  = decltype(ic)::value;
+        const uint32_t lo = pos_base<ro, 2 * i>(L) + pos_imm<ro, 2 * i>();
+        const uint32_t hi = (2 * i + 1 < ro.npos) ? pos_base<ro, 2 * i + 1>(L) + pos_imm<ro, 2 * i + 1>() : 0U;
+        if (L.wave < P2_WAVES) {
+          gdst[static_cast<uint32_t>(K0 + i) * WG + static_cast<uint32_t>(L.wave * 64 + L.lane)] =
+              (lo & 0xffffU) | (hi << 16);
+        }
+      });
+    }
+  }
   static __device__ __forceinline__ void write_split_table(uint32_t* gdst, int wave, int lane)
   {
-    lanes L = make_lanes<false>(wave, lane, 64, 0U);
-    fill_split(L, std::make_integer_sequence<int, G.n_steps>{}, gdst);
+    const lanes L = make_lanes(wave, lane, 64, 0U);
+    static_for<G.n_steps>([&](auto sc) __attribute__((always_inline)) {
+      write_split_step<decltype(sc)::value>(gdst, L);
+    });
   }
 };
 
@@ -1461,20 +1228,19 @@ struct qdec {
   static constexpr int      Z       = G.Z;
   static constexpr int      NS      = Q.slots;
   static constexpr uint32_t WG      = static_cast<uint32_t>(Q.waves) * 64U; /* table stride: lanes per workgroup */
-  static constexpr uint32_t SCRATCH = static_cast<uint32_t>(SB * G.N_full) * static_cast<uint32_t>(Z);
-  static_assert(Q.valid && SCRATCH + SB * Z <= 65535U, "lane-split schedule: 16-bit LDS addresses");
+  static constexpr uint32_t SCRATCH = static_cast<uint32_t>(G.N_full) * static_cast<uint32_t>(Z);
+  static_assert(Q.valid && SCRATCH + Z <= 65535U, "lane-split schedule: 16-bit LDS addresses");
   using cr_t = uint32_t[NS];
 
   struct qlanes {
-    uint32_t one2, onef;
+    uint32_t one2; /* lanes::one2 */
     int      nof_layers, grp;
     bool     act2, act1; /* this lane's check node exists (t < Z) in a two-row / a single-row step */
   };
   static __device__ __forceinline__ qlanes make_lanes(int wave, int lane, int nof_layers)
   {
     qlanes L{};
-    L.one2       = opaque_s(SB == 2 ? 0x80008000U : 0x00010001U);
-    L.onef       = opaque_s(0x3c003c00U);
+    L.one2       = opaque_s(0x00010001U);
     L.nof_layers = nof_layers;
     L.grp        = wave < Q.WH ? 0 : 1;
     L.act2       = ((wave - L.grp * Q.WH) * 64 + lane) / Q.P2 < Z;
@@ -1515,7 +1281,7 @@ struct qdec {
         const int j = 2 * q + h, e = k + P * j;
         a[h]        = SCRATCH;
         if (t < Z && j < npos && e < deg) {
-          a[h] = static_cast<uint32_t>(SB * (col[e] * Z + (t + sh[e]) % Z));
+          a[h] = static_cast<uint32_t>(col[e] * Z + (t + sh[e]) % Z);
         }
       }
       dst[static_cast<uint32_t>(st.q0 + q) * WG + static_cast<uint32_t>(wave * 64 + lane)] = a[0] | (a[1] << 16);
@@ -1544,8 +1310,8 @@ struct qdec {
       const uint32_t w = opaque(tab[Q0 + i]); /* read in the step: not hoisted out of the iteration loop */
       base[2 * i]      = w & 0xffffU;
       base[2 * i + 1]  = w >> 16;
-      lo[i]            = rds(base[2 * i], 0);
-      hi[i]            = (2 * i + 1 < ro.npos) ? rds(base[2 * i + 1], 0) : SOFT_INF;
+      lo[i]            = rd8(base[2 * i], 0);
+      hi[i]            = (2 * i + 1 < ro.npos) ? rd8(base[2 * i + 1], 0) : SOFT_INF;
     });
     SPEC_STAMP_FULL(S, 1);
     u16x2    M1 = splatu(MIN_START), M2 = splatu(MIN_START);
@@ -1572,13 +1338,13 @@ struct qdec {
     uint32_t snv[NP];
     static_for<NP>([&](auto ic) __attribute__((always_inline)) {
       constexpr int i = decltype(ic)::value;
-      pass2(Gs[i], A[i], N1, CC, PP, cr[Q0 + i], snv[i], L.onef);
+      pass2(Gs[i], A[i], N1, CC, PP, cr[Q0 + i], snv[i]);
     });
     static_for<NP>([&](auto ic) __attribute__((always_inline)) {
       constexpr int i = decltype(ic)::value;
-      wrs(base[2 * i], 0, snv[i]);
+      wr8(base[2 * i], 0, snv[i]);
       if constexpr (2 * i + 1 < ro.npos) {
-        wrs(base[2 * i + 1], 0, snv[i] >> 16);
+        wr8(base[2 * i + 1], 0, snv[i] >> 16);
       }
     });
   }
@@ -1622,270 +1388,6 @@ struct qdec {
   }
 };
 
-/* ---- register-resident decoder of the one-wave graphs (spec::rgraph, ldpc_spec.h) ---------------------------------
- * One wave per codeblock, lane t = check node t of the row being updated (lanes t >= Z: duplicates when Z divides 64,
- * don't-cares otherwise). sv[c]: column c's register (rotation and half per the compile-time state); cr: the c2v
- * pairs of every row (pair i of row r at cr[q0 + i]). A read at rotation k is one ds_bpermute_b32 from lane
- * (t + k) mod Z: when Z divides 64 the address 4 t + 4 k wraps by itself (ds_bpermute uses address bits [7:2]) and the
- * constant goes into the instruction offset; otherwise the address is byte k % 4 of the lane's rotation table word
- * rt[k / 4] (4 ((t + k) mod Z) for each k, built once per codeblock), at most one shift. */
-#ifndef LDPC_SPEC_REG_SCHED_BARRIER
-#define LDPC_SPEC_REG_SCHED_BARRIER 1
-#endif
-template <const spec::sgraph& G, const spec::rgraph& R>
-struct rdec {
-  static constexpr int  Z    = G.Z;
-  static constexpr int  NC   = G.N_full;
-  static constexpr int  NP   = R.n_pairs;
-  static constexpr bool POW2 = (64 % Z) == 0;
-  static constexpr int  NRT  = POW2 ? 1 : (Z + 3) / 4;
-  static_assert(R.valid && NP > 0, "register-resident schedule");
-  static_assert(SB == 1, "register-resident decoder: int8 soft bits (build with -DLDPC_SPEC_F16=0)");
-  using sv_t = uint32_t[NC];
-  using cr_t = uint32_t[NP];
-
-  struct rlanes {
-    uint32_t t4;      /* 4 * lane */
-    uint32_t rt[NRT]; /* byte j of rt[q]: 4 ((lane + 4 q + j) mod Z) (Z not dividing 64) */
-    uint32_t one2, c121;
-    int      nl; /* the codeblock's layer count (uniform) */
-  };
-  static __device__ __forceinline__ rlanes make_lanes(int lane, int nl)
-  {
-    rlanes L{};
-    L.t4 = 4U * static_cast<uint32_t>(lane);
-    if constexpr (!POW2) {
-      for (int q = 0; q < NRT; ++q) {
-        uint32_t w = 0;
-        for (int j = 0; j < 4; ++j) {
-          w |= (4U * static_cast<uint32_t>((lane + 4 * q + j) % Z)) << (8 * j);
-        }
-        L.rt[q] = w;
-      }
-    } else {
-      L.rt[0] = 0;
-    }
-    L.one2 = opaque_s(0x00010001U);
-    L.c121 = opaque_s(121U);
-    L.nl   = nl;
-    return L;
-  }
-
-  template <int K>
-  static __device__ __forceinline__ uint32_t rot(uint32_t v, const rlanes& L)
-  {
-    if constexpr (K == 0) {
-      return v;
-    } else if constexpr (POW2) {
-      return static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(static_cast<int>(L.t4 + 4U * K), static_cast<int>(v)));
-    } else {
-      constexpr int  q = K / 4, j = K % 4;
-      const uint32_t a = j == 0 ? L.rt[q] : (L.rt[q] >> (8 * j));
-      return static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(static_cast<int>(a), static_cast<int>(v)));
-    }
-  }
-  /* v_perm selector: the low half from byte pair h0 of src1, the high half from byte pair h1 of src0 */
-  static constexpr uint32_t psel(int h0, int h1)
-  {
-    return static_cast<uint32_t>((2 * h0) | ((2 * h0 + 1) << 8) | ((4 + 2 * h1) << 16) | ((5 + 2 * h1) << 24));
-  }
-
-  /* the lane words pass through opaque asm once per row, in place (a copy would cost a v_mov per word and row):
-   * every rotation address derived from them is iteration-invariant, and hoisted out of the iteration loop they
-   * would hold a register per rotation */
-  static __device__ __forceinline__ void opaque_lanes(rlanes& L)
-  {
-    asm volatile("" : "+v"(L.t4));
-    for (int q = 0; q < NRT; ++q) {
-      asm volatile("" : "+v"(L.rt[q]));
-    }
-  }
-
-  template <int RI, bool MASK>
-  static __device__ __forceinline__ void row(sv_t& sv, cr_t& cr, rlanes& L)
-  {
-    opaque_lanes(L);
-    static constexpr spec::rrow rw  = R.rows[RI];
-    constexpr int               NPR = (rw.deg + 1) / 2;
-    uint32_t                    Gs[NPR], A[NPR];
-    u16x2                       M1 = splatu(MIN_START), M2 = splatu(MIN_START);
-    uint32_t                    SX = 0;
-    static_for<NPR>([&](auto ic) __attribute__((always_inline)) {
-      constexpr int  i   = decltype(ic)::value;
-      constexpr bool two = 2 * i + 1 < rw.deg;
-      constexpr int  j1  = two ? 2 * i + 1 : 2 * i;
-      constexpr int  c0 = rw.e[2 * i].col, k0 = rw.e[2 * i].k, h0 = rw.e[2 * i].half, g0 = rw.e[2 * i].reg;
-      constexpr int  c1 = rw.e[j1].col, k1 = rw.e[j1].k, h1 = two ? rw.e[j1].half : 0, g1 = rw.e[j1].reg;
-      uint32_t       S;
-      if constexpr (two && g0 == g1 && k0 == k1 && h0 == 0 && h1 == 1) {
-        S = rot<k0>(sv[c0], L); /* both edges' columns in one register, same rotation: already the pair */
-      } else {
-        const uint32_t v0 = rot<k0>(sv[c0], L);
-        uint32_t       v1 = L.c121; /* no second edge: +infinity */
-        if constexpr (two) {
-          v1 = rot<k1>(sv[c1], L);
-        }
-        S = __builtin_amdgcn_perm(v1, v0, psel(h0, h1));
-      }
-      pass1(S, cr[rw.q0 + i], M1, M2, SX, Gs[i], A[i], L.one2);
-    });
-    uint32_t m1, m2, sx;
-    fold_halves(M1, M2, SX, m1, m2, sx);
-    uint32_t n1 = (__umul24(m1, 52432U) + 26216U) >> 16; /* round(0.8 m), gen.cpp:70-79 */
-    uint32_t cc = ((__umul24(m2, 52432U) + 26216U) >> 16) + m1;
-    if constexpr (MASK && RI >= 4) { /* a row beyond the layer count (nl >= 4 always) updates to the identity */
-      /* opaque: hoisted out of the iteration loop, the 38 row tests became spilled 64-bit masks and v_cndmask */
-      const uint32_t act = RI < static_cast<int>(opaque_s(static_cast<uint32_t>(L.nl))) ? ~0U : 0U;
-      n1 &= act;
-      cc &= act;
-    }
-    const s16x2 N1 = splat(static_cast<int>(n1));
-    const s16x2 CC = splat(static_cast<int>(cc));
-    const s16x2 PP = splat(static_cast<short>(sx | 1U));
-    static_for<NPR>([&](auto ic) __attribute__((always_inline)) {
-      constexpr int i = decltype(ic)::value;
-      uint32_t      sn;
-      pass2(Gs[i], A[i], N1, CC, PP, cr[rw.q0 + i], sn, 0U);
-      sv[rw.e[2 * i].col] = sn;
-      if constexpr (2 * i + 1 < rw.deg) {
-        sv[rw.e[2 * i + 1].col] = sn;
-      }
-    });
-#if LDPC_SPEC_REG_SCHED_BARRIER
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-  }
-
-  static constexpr int chunk_begin(int x) { return x == 0 ? 0 : R.exit_row[x - 1]; }
-  static constexpr int chunk_end(int x) { return x < R.n_exits ? R.exit_row[x] : G.M; }
-
-  /* leaving the iteration before row exit_row[XI]: every column the rest of the iteration would have written goes
-   * to its boundary state (rotation, half, and the register it shares with its boundary partner) */
-  template <int XI>
-  static __device__ __forceinline__ void fixup(sv_t& sv, rlanes& L)
-  {
-    opaque_lanes(L);
-    static_for<NC>([&](auto ccn) __attribute__((always_inline)) {
-      constexpr int c    = decltype(ccn)::value;
-      constexpr int p    = R.partner[c];
-      constexpr int pp   = p < 0 ? c : p;
-      constexpr int k    = (R.end[c].rho - R.at_exit[XI][c].rho + Z) % Z;
-      constexpr int kp   = (R.end[pp].rho - R.at_exit[XI][pp].rho + Z) % Z;
-      constexpr int ch   = R.at_exit[XI][c].half, eh = R.end[c].half, chp = R.at_exit[XI][pp].half;
-      if constexpr (R.at_exit[XI][c].reg != R.end[c].reg && (p < 0 || eh == 0)) {
-        const uint32_t v = rot<k>(sv[c], L);
-        if constexpr (p < 0) {
-          sv[c] = ch == eh ? v : (eh != 0 ? (v << 16) : (v >> 16));
-        } else {
-          const uint32_t vp = rot<kp>(sv[p], L);
-          const uint32_t w  = __builtin_amdgcn_perm(vp, v, psel(ch, chp));
-          sv[c]                     = w;
-          sv[p]                     = w;
-        }
-      }
-    });
-  }
-
-  template <int B, bool MASK, int... I>
-  static __device__ __forceinline__ void rows_impl(sv_t& sv, cr_t& cr, rlanes& L, std::integer_sequence<int, I...>)
-  {
-    (row<B + I, MASK>(sv, cr, L), ...);
-  }
-  template <int X>
-  static __device__ __forceinline__ bool chunk(sv_t& sv, cr_t& cr, rlanes& L)
-  {
-    if constexpr (X > 0) {
-      if (chunk_begin(X) >= static_cast<int>(opaque_s(static_cast<uint32_t>(L.nl)))) {
-        fixup<X - 1>(sv, L);
-        return false;
-      }
-    }
-    rows_impl<chunk_begin(X), true>(sv, cr, L, std::make_integer_sequence<int, chunk_end(X) - chunk_begin(X)>{});
-    return true;
-  }
-  template <int... X>
-  static __device__ __forceinline__ void iteration_impl(sv_t& sv, cr_t& cr, rlanes& L,
-                                                        std::integer_sequence<int, X...>)
-  {
-    (void)(chunk<X>(sv, cr, L) && ...);
-  }
-  /* a codeblock with fewer layers than rows: chunks, exits and identity rows */
-  static __device__ __forceinline__ void iteration_partial(sv_t& sv, cr_t& cr, rlanes& L)
-  {
-    iteration_impl(sv, cr, L, std::make_integer_sequence<int, R.n_exits + 1>{});
-  }
-  /* every row a layer (nl == M): one straight-line block, no exits, no masks */
-  static __device__ __forceinline__ void iteration(sv_t& sv, cr_t& cr, rlanes& L)
-  {
-    rows_impl<0, false>(sv, cr, L, std::make_integer_sequence<int, G.M>{});
-  }
-
-  /* the registers in their boundary state from the soft bits in LDS (column c at c Z) */
-  static __device__ __forceinline__ void load(sv_t& sv, int lane)
-  {
-    const int tz = POW2 ? (lane & (Z - 1)) : lane;
-    static_for<NC>([&](auto ccn) __attribute__((always_inline)) {
-      constexpr int c    = decltype(ccn)::value;
-      constexpr int rho  = R.end[c].rho, half = R.end[c].half;
-      constexpr int p    = R.partner[c];
-      constexpr int rhop = p < 0 ? 0 : R.end[p < 0 ? 0 : p].rho;
-      if constexpr (p < 0 || half == 0) {
-        const uint32_t va = static_cast<uint32_t>(rd8(static_cast<uint32_t>((tz + rho) % Z), c * Z));
-        if constexpr (p < 0) {
-          sv[c] = half != 0 ? (va << 16) : va;
-        } else {
-          const uint32_t vb = static_cast<uint32_t>(rd8(static_cast<uint32_t>((tz + rhop) % Z), p * Z));
-          const uint32_t w  = __builtin_amdgcn_perm(vb, va, 0x05040100U);
-          sv[c]             = w;
-          sv[p]             = w;
-        }
-      }
-    });
-  }
-  /* Early stop from the registers (the check of impl.cpp:126-134 without the LDS hard-decision and CRC passes, whose
-   * registers on top of the decoder's spilled it): hard bit = soft <= 0 (llr.cpp:226-252), any zero soft bit of the
-   * K Z systematic ones fails, and the CRC of the first Lsig hard bits (zero-init, MSB first) is linear in them: lane t
-   * keeps, per systematic column c, the remainder x^(Lsig - 1 - i + order) mod G of its bit i = c Z + (t + rho_c) mod Z
-   * (zero for i >= Lsig and for lanes t >= Z), and the check XORs the ones of its set bits over the wave. */
-  using ec_t = uint32_t[G.K];
-  static __device__ __forceinline__ void et_setup(ec_t& ec, int lane, int Lsig, int order, const uint32_t* xpow)
-  {
-    static_for<G.K>([&](auto ccn) __attribute__((always_inline)) {
-      constexpr int c = decltype(ccn)::value;
-      constexpr int rho = R.end[c].rho;
-      const int     i   = c * Z + (lane + rho) % Z;
-      ec[c]             = (lane < Z && i < Lsig) ? xpow[Lsig - 1 - i + order] : 0U;
-    });
-  }
-  static __device__ __forceinline__ bool et_check(const sv_t& sv, const ec_t& ec, int lane)
-  {
-    uint32_t acc = 0, zero = 0;
-    static_for<G.K>([&](auto ccn) __attribute__((always_inline)) {
-      constexpr int c    = decltype(ccn)::value;
-      constexpr int half = R.end[c].half;
-      const int     v    = half != 0 ? (static_cast<int>(sv[c]) >> 16) : static_cast<int>(static_cast<short>(sv[c]));
-      acc ^= v <= 0 ? ec[c] : 0U;
-      zero |= v == 0 ? 1U : 0U;
-    });
-    /* uniform (readfirstlane, ballot): a per-lane condition would make the loop exit divergent, and the compiler
-     * then keeps every loop-carried register twice (spilled) */
-    acc = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(wave_xor(acc))));
-    return __builtin_amdgcn_ballot_w64(zero != 0U && lane < Z) == 0 && acc == 0U;
-  }
-
-  /* the systematic columns' soft bits back into LDS (the hard decision reads [0, K Z)) */
-  static __device__ __forceinline__ void store_systematic(const sv_t& sv, int lane)
-  {
-    if (lane < Z) {
-      static_for<G.K>([&](auto ccn) __attribute__((always_inline)) {
-        constexpr int c = decltype(ccn)::value;
-        constexpr int rho = R.end[c].rho, half = R.end[c].half;
-        wr8(static_cast<uint32_t>((lane + rho) % Z), c * Z, half != 0 ? (sv[c] >> 16) : sv[c]);
-      });
-    }
-  }
-};
-
 } // namespace sp
 
 } // namespace
@@ -1924,8 +1426,6 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
   if (static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_i8*)s_soft)) != 0U || lay.soft != 0U) {
     __builtin_trap(); /* lds_byte() would address the wrong bytes */
   }
-  uint16_t* s_soft16 = reinterpret_cast<uint16_t*>(smem); /* binary16 soft bits (specialised kernels, SOFT_BYTES = 2) */
-  constexpr bool F16 = SPEC_ID >= 0 && spec::SOFT_BYTES == 2;
   int8_t*   s_c2v  = reinterpret_cast<int8_t*>(smem + lay.c2v);
   uint8_t*  s_hb   = smem + lay.hard;
   uint32_t* s_red  = reinterpret_cast<uint32_t*>(smem + lay.red);
@@ -2007,9 +1507,7 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
   using SD                = sp::dec<SG::g>;
   /* one-wave graphs: the lane-split decoder (sp::qdec); its address table comes into registers here, its loads in
    * flight with the LLRs' (the same words for every codeblock of a launch: L2-resident after the first) */
-  /* one-wave graphs on the register-resident decoder (sp::rdec): soft bits and c2v in registers, no tables */
-  constexpr bool REG      = SPEC && spec::is_reg(SG::g);
-  constexpr bool QUAD     = SPEC && !REG && spec::is_quad(SG::g);
+  constexpr bool QUAD     = SPEC && spec::is_quad(SG::g);
   constexpr int  QN       = QUAD ? SG::q.slots : 1;
   using QD                = sp::qdec<SG::g, SG::q>;
   uint32_t      qtab[QN];
@@ -2020,7 +1518,7 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
       qtab[q] = gq[static_cast<uint32_t>(q) * QD::WG + static_cast<uint32_t>(tid)];
     }
   }
-  constexpr int SPLIT_U4  = (SPEC && !QUAD && !REG && LDPC_SPEC_SPLIT_COPY) ? SD::LDS_PAIRS * static_cast<int>(SD::WG) / 4 : 0;
+  constexpr int SPLIT_U4  = (SPEC && !QUAD) ? SD::LDS_PAIRS * static_cast<int>(SD::WG) / 4 : 0;
   constexpr int SPLIT_PER = 5; /* loads per thread: LDS_PAIRS / 4 at the decoder's own width */
   uint4         stv[SPLIT_PER];
   if constexpr (SPLIT_U4 > 0) {
@@ -2073,13 +1571,12 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
     const int n4 = (static_cast<int>(lay.soft_stride) + 3) / 4; /* whole column (the layout leaves 64 bytes of slack) */
     int*      sc = reinterpret_cast<int*>(s_soft + static_cast<int>(lay.soft_stride) * N_full);
     for (int i = tid; i < n4; i += nthr) {
-      sc[i] = F16 ? 0x57905790 : 0x79797979; /* 121.0 in binary16 / 121 = 0x79 in every byte */
+      sc[i] = 0x79797979; /* 121 = 0x79 in every byte */
     }
   } else {
-    /* edge table: per row EDGE_SLOT words, padded with dummy edges at the scratch bytes after the soft columns.
-     * Generic: shift | (col * Z) << 16. Specialised: col * 4Z + shift (byte offset of the copy at column offset 0). */
+    /* edge table: per row EDGE_SLOT words shift | (col * Z) << 16, padded with dummy edges at the scratch bytes after
+     * the soft columns */
     uint32_t*      s_edges = reinterpret_cast<uint32_t*>(smem + lay.edges);
-    constexpr bool copies4 = false;
     const uint32_t dummy   = static_cast<uint32_t>(graph->N_full) * graph->Z << 16;
     for (int i = tid; i < graph->M * EDGE_SLOT; i += nthr) {
       const int      r   = i / EDGE_SLOT, k = i - r * EDGE_SLOT;
@@ -2087,7 +1584,7 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
       uint32_t       w   = dummy;
       if (k < static_cast<int>(rw >> 16)) {
         const uint32_t ew = graph->edges[(rw & 0xffffU) + k];
-        w = copies4 ? (ew & 0xffffU) * 4U + (ew >> 16) : (ew >> 16) | ((ew & 0xffffU) << 16);
+        w = (ew >> 16) | ((ew & 0xffffU) << 16);
       }
       s_edges[i] = w;
     }
@@ -2131,19 +1628,7 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
           }
           v = make_uint4(clamp_inf4(v.x), clamp_inf4(v.y), clamp_inf4(v.z), clamp_inf4(v.w));
         }
-        if constexpr (F16) { /* 16 LLRs -> 32 bytes */
-          const uint2 a = soft_f16x4(v.x), b = soft_f16x4(v.y), c = soft_f16x4(v.z), e = soft_f16x4(v.w);
-          s4[2 * i]     = make_uint4(a.x, a.y, b.x, b.y);
-          s4[2 * i + 1] = make_uint4(c.x, c.y, e.x, e.y);
-        } else if constexpr (SPEC && spec::SOFT_COPIES == 4) {
-          /* the two copies the specialised decoder reads (column offsets Z and 2Z); Z % 16 == 0 */
-          const int col = (16 * i) / Z, o = 16 * i - col * Z;
-          uint4*    c4  = reinterpret_cast<uint4*>(s_soft + col * static_cast<int>(lay.soft_stride) + Z + o);
-          c4[0]         = v;
-          c4[Z / 16]    = v;
-        } else {
-          s4[i] = v;
-        }
+        s4[i] = v;
       }
       base4 += PRO_U * nthr;
       if (base4 >= t4) {
@@ -2155,7 +1640,7 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
         pv[u]       = (i >= z4 && i < z4 + l4 && i < t4) ? g4[i - z4] : make_uint4(0, 0, 0, 0);
       }
     }
-  } else if (!(SPEC && spec::SOFT_COPIES == 4) && (reinterpret_cast<uintptr_t>(llr) & 15U) == 0) {
+  } else if ((reinterpret_cast<uintptr_t>(llr) & 15U) == 0) {
     /* 16-byte loads whatever the alignment of 2Z and L (Z % 8 != 0, e.g. BG2 Z=36, or shortened lengths): the chunks
      * land at soft + 2Z + 16 k through 4-byte (Z even) or 2-byte LDS writes, the last L % 16 LLRs by byte loads, and
      * a thread issues all its loads of a pass (and the tail's) before storing any. A loop of byte loads instead paid
@@ -2166,18 +1651,10 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
       tv = llr[16 * lc + tid];
     }
     for (int i = tid; i < 2 * Z; i += nthr) {
-      if constexpr (F16) {
-        s_soft16[i] = 0;
-      } else {
-        s_soft[i] = 0;
-      }
+      s_soft[i] = 0;
     }
     for (int i = 2 * Z + L + tid; i < total; i += nthr) {
-      if constexpr (F16) {
-        s_soft16[i] = 0;
-      } else {
-        s_soft[i] = 0;
-      }
+      s_soft[i] = 0;
     }
     for (int c0 = 0; c0 < lc; c0 += PRO_U * nthr) {
       uint4 w[PRO_U];
@@ -2205,11 +1682,7 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const uint32_t c = clamp_inf4(wv[q]);
-          if constexpr (F16) { /* element 2Z + 16 k + 4 q: byte 4 Z + 32 k + 8 q, 4-byte aligned */
-            const uint2 h                                      = soft_f16x4(c);
-            reinterpret_cast<uint32_t*>(s_soft16 + 2 * Z + 16 * k)[2 * q]     = h.x;
-            reinterpret_cast<uint32_t*>(s_soft16 + 2 * Z + 16 * k)[2 * q + 1] = h.y;
-          } else if ((Z & 1) == 0) {
+          if ((Z & 1) == 0) {
             reinterpret_cast<uint32_t*>(dst)[q] = c;
           } else {
             reinterpret_cast<uint16_t*>(dst)[2 * q]     = static_cast<uint16_t>(c);
@@ -2223,11 +1696,7 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
       if (tv != 0) {
         last_local = max(last_local, li + 1);
       }
-      if constexpr (F16) {
-        s_soft16[2 * Z + li] = soft_f16(med3i(tv, -LLR_INTERNAL_INF, LLR_INTERNAL_INF));
-      } else {
-        s_soft[2 * Z + li] = static_cast<int8_t>(med3i(tv, -LLR_INTERNAL_INF, LLR_INTERNAL_INF));
-      }
+      s_soft[2 * Z + li] = static_cast<int8_t>(med3i(tv, -LLR_INTERNAL_INF, LLR_INTERNAL_INF));
     }
   } else {
     for (int i = tid; i < total; i += nthr) {
@@ -2240,15 +1709,7 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
         }
         v = static_cast<int8_t>(med3i(v, -LLR_INTERNAL_INF, LLR_INTERNAL_INF));
       }
-      if constexpr (F16) {
-        s_soft16[i] = soft_f16(v);
-      } else if constexpr (SPEC && spec::SOFT_COPIES == 4) {
-        const int col = i / Z, o = i - col * Z;
-        s_soft[col * static_cast<int>(lay.soft_stride) + Z + o]     = v;
-        s_soft[col * static_cast<int>(lay.soft_stride) + 2 * Z + o] = v;
-      } else {
-        s_soft[i] = v;
-      }
+      s_soft[i] = v;
     }
   }
   CB_STAMP(7); /* diagnostic build: the soft bits' loads have returned and are stored */
@@ -2334,35 +1795,14 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
       q = 0;
     }
     sp::lanes sl{};
-    if constexpr (!QUAD && !REG) {
-      sl = SD::template make_lanes<SPEC>(wave, lane, __builtin_amdgcn_readfirstlane(nof_layers),
+    if constexpr (!QUAD) {
+      sl = SD::make_lanes(wave, lane, __builtin_amdgcn_readfirstlane(nof_layers),
                                         lay.c2v + 4U * static_cast<uint32_t>(tid));
     }
     typename SD::pf_t pf = {0, 0, 0, 0, 0};
-    if constexpr (SPEC && !QUAD && !REG) {
+    if constexpr (SPEC && !QUAD) {
       SD::template load_pf<0>(pf, sl);
       SD::ext_init(cr, sl); /* the extension edges kept in registers: their state from the soft bits, once */
-    }
-    using RD = sp::rdec<SG::g, SG::r>;
-    uint32_t rsv[REG ? SG::g.N_full : 1]; /* register-resident decoder: the columns' registers */
-    uint32_t rcr[REG ? SG::r.n_pairs : 1]; /* ... and the c2v pairs */
-    for (auto& q : rcr) {
-      q = 0;
-    }
-    auto rl = [&] {
-      if constexpr (REG) {
-        return RD::make_lanes(lane, __builtin_amdgcn_readfirstlane(nof_layers));
-      } else {
-        return 0;
-      }
-    }();
-    uint32_t rec[REG ? SG::g.K : 1]; /* register-resident decoder: the early-stop CRC terms (RD::et_setup) */
-    if constexpr (REG) {
-      RD::load(rsv, lane);
-      if (d.crc_mode == LDPC_HIP_CRC_MODE_EARLY_STOP) {
-        RD::et_setup(rec, lane, Lsig, d.crc_poly == LDPC_HIP_CRC16 ? 16 : 24,
-                     crc_tables + CRC_XPOW_OFFSET + d.crc_poly * CRC_XPOW_WORDS);
-      }
     }
     uint32_t qcr[QN]; /* lane-split decoder: this lane's c2v pairs */
     for (auto& q : qcr) {
@@ -2449,14 +1889,10 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
       }
       hb_current = false;
       if (d.crc_mode == LDPC_HIP_CRC_MODE_EARLY_STOP) {
-        bool ok;
-        if constexpr (F16) {
-          ok = block_hard_decision16(s_soft, s_hb, KZ, &s_red[30], static_cast<uint32_t>(it) + 1U);
-        } else {
-          ok = block_hard_decision<SPEC ? SG::g.Z : 0>(s_soft, s_hb, KZ, &s_red[30], static_cast<uint32_t>(it) + 1U, Z,
-                                                       SPEC ? static_cast<int>(lay.soft_stride) : 0,
-                                                       static_cast<int>(lay.soft_read));
-        }
+        const bool ok =
+            block_hard_decision<SPEC ? SG::g.Z : 0>(s_soft, s_hb, KZ, &s_red[30], static_cast<uint32_t>(it) + 1U, Z,
+                                                    SPEC ? static_cast<int>(lay.soft_stride) : 0,
+                                                    static_cast<int>(lay.soft_read));
         hb_current    = true;
         if (ok && block_crc(s_hb, Lsig, d.crc_poly, s_crct,
                             s_red, crc_tables + CRC_MCOL_OFFSET + d.crc_poly * CRC_MCOL_WORDS) == 0) {
@@ -2467,35 +1903,7 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
       }
     }
     };
-    /* The register-resident decoder's loop: two copies, full-length codeblocks without the layer checks. The early
-     * stop ends it through the loop condition */
-    auto reg_loop = [&](auto partial) __attribute__((always_inline)) {
-      /* uniform by construction (the descriptor may come through vector loads): a divergent loop exit makes the
-       * compiler keep every loop-carried register twice */
-      int        n  = __builtin_amdgcn_readfirstlane(static_cast<int>(d.max_iterations));
-      const bool et = __builtin_amdgcn_readfirstlane(static_cast<int>(d.crc_mode)) == LDPC_HIP_CRC_MODE_EARLY_STOP;
-      for (int it = 0; it < n && REG; ++it) {
-        if constexpr (REG) {
-          if constexpr (decltype(partial)::value) {
-            RD::iteration_partial(rsv, rcr, rl);
-          } else {
-            RD::iteration(rsv, rcr, rl);
-          }
-          if (et && RD::et_check(rsv, rec, lane)) {
-            has_value  = 1;
-            iterations = it + 1;
-            n          = it + 1;
-          }
-        }
-      }
-    };
-    if constexpr (REG) {
-      if (nof_layers < SG::g.M) {
-        reg_loop(std::true_type{});
-      } else {
-        reg_loop(std::false_type{});
-      }
-    } else if constexpr (SPEC && !QUAD && !REG && SD::HAS_PARTIAL) {
+    if constexpr (SPEC && !QUAD && SD::HAS_PARTIAL) {
       if (__builtin_expect(nof_layers <= SD::PARTIAL_LAYERS, 0)) {
         run_iterations(std::true_type{});
       } else {
@@ -2506,17 +1914,9 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
     }
     CB_STAMP(3);
     if (!hb_current) {
-      if constexpr (REG) {
-        RD::store_systematic(rsv, lane);
-        __syncthreads();
-      }
-      if constexpr (F16) {
-        block_hard_decision16(s_soft, s_hb, KZ, &s_red[30], 0xffffffffU);
-      } else {
-        block_hard_decision<SPEC ? SG::g.Z : 0>(s_soft, s_hb, KZ, &s_red[30], 0xffffffffU, Z,
-                                                SPEC ? static_cast<int>(lay.soft_stride) : 0,
-                                                static_cast<int>(lay.soft_read));
-      }
+      block_hard_decision<SPEC ? SG::g.Z : 0>(s_soft, s_hb, KZ, &s_red[30], 0xffffffffU, Z,
+                                              SPEC ? static_cast<int>(lay.soft_stride) : 0,
+                                              static_cast<int>(lay.soft_read));
     }
     if (d.crc_mode == LDPC_HIP_CRC_MODE_CHECK_AFTER) {
       has_value = (block_crc(s_hb, Lsig, d.crc_poly, s_crct,
@@ -2542,16 +1942,11 @@ __device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const
 #undef graph
 }
 
-/* threads per workgroup at most: the generic body 16 waves, a specialised one 12 (up to 168 VGPRs), the
- * register-resident decoder one wave (up to 256 VGPRs) */
+/* threads per workgroup at most: the generic body 16 waves, a specialised one 12 (up to 168 VGPRs) */
 template <int SPEC_ID>
 constexpr int decode_max_threads()
 {
-  if constexpr (SPEC_ID < 0) {
-    return 1024;
-  } else {
-    return spec::is_reg(spec::spec_graph<SPEC_ID>::g) ? 64 : 768;
-  }
+  return SPEC_ID < 0 ? 1024 : 768;
 }
 
 template <bool SF08, int SPEC_ID>
@@ -2803,8 +2198,7 @@ __global__ void __launch_bounds__(768) ldpc_split_table_kernel(uint32_t* __restr
 {
   using SG = spec::spec_graph<SPEC_ID>;
   using SD = sp::dec<SG::g>;
-  if constexpr (spec::is_reg(SG::g)) { /* the register-resident decoder has no table */
-  } else if constexpr (spec::is_quad(SG::g)) { /* the lane-split decoder's address table (sp::qdec) */
+  if constexpr (spec::is_quad(SG::g)) { /* the lane-split decoder's address table (sp::qdec) */
     sp::qdec<SG::g, SG::q>::write_table(dst, static_cast<int>(threadIdx.x >> 6), static_cast<int>(threadIdx.x & 63),
                                         std::make_integer_sequence<int, SG::q.n_steps>{});
   } else if constexpr (SD::LDS_PAIRS > 0) {

@@ -22,12 +22,12 @@ const base_edge k_base_edges[] = {
 
 uint32_t align16(uint32_t x) { return (x + 15U) & ~15U; }
 
-/* A single-row step splits each check node's edges over two lanes when the row degree reaches this value (timed in
- * round 1: thresholds 7-11 were 1-3% slower on C2). The specialised schedules have their own (ldpc_spec.h). */
-#ifndef LDPC_SPEC_SPLIT_MIN_DEGREE
-#define LDPC_SPEC_SPLIT_MIN_DEGREE 6
-#endif
-constexpr unsigned split_min_degree() { return LDPC_SPEC_SPLIT_MIN_DEGREE; }
+/* The generic kernel's schedule: a single-row step splits each check node's edges over two lanes when the row degree
+ * reaches this value. This file used to give 6 behind an #ifndef of a macro that ldpc_spec.h had already defined as 12,
+ * so the generic kernel has used 12 since that header came first in the include order. The round-1 timing once quoted
+ * here (1-3% slower on C2) was of thresholds 7-11 against 6; 12 was not timed on the generic kernel. Changing the value
+ * changes the generic kernel's task tables. The specialised schedules have their own (spec::SPLIT_MIN_DEGREE). */
+constexpr unsigned GENERIC_SPLIT_MIN_DEGREE = 12;
 
 } // namespace
 
@@ -139,7 +139,7 @@ bool build_graph(int bg, unsigned Z, graph_desc& g)
     }
     /* a single-row step splits each check node's edges over two lanes to keep every SIMD busy */
     const unsigned deg   = g.rows[m] >> 16;
-    const bool     split = (nr == 1) && deg >= split_min_degree();
+    const bool     split = (nr == 1) && deg >= GENERIC_SPLIT_MIN_DEGREE;
     g.groups[ng++]       = m | (nr << 8) | ((split ? 2U : 1U) << 16);
     maxg           = std::max(maxg, nr);
     m += nr;
@@ -158,22 +158,18 @@ lds_layout make_lds_layout(const graph_desc& g, bool spec)
   uint32_t   off = 0;
   l.soft         = off; /* must stay 0: the decode kernel addresses soft bits from the LDS base */
   if (spec) {
-    /* specialised kernel: spec::SOFT_COPIES copies per column, c2v in registers (ldpc_hip_kernels.hip, namespace sp) */
-    l.soft_stride = static_cast<uint32_t>(spec::SOFT_COPIES * spec::SOFT_BYTES) * g.Z; /* bytes per column */
-    l.soft_read   = spec::SOFT_COPIES == 1 ? 0U : g.Z;
+    /* specialised kernel: one int8 copy per column, c2v in registers (ldpc_decode_body.h, namespace sp) */
+    l.soft_stride = g.Z; /* bytes per column */
+    l.soft_read   = 0;
     off += align16(static_cast<uint32_t>(g.N_full + 1) * l.soft_stride + 64); /* + one column of dummy-edge scratch */
     l.c2v = off; /* c2v lives in registers; the region holds the split rows' address table (BG1 rows 0-3) */
     int  qid = -1; /* a one-wave graph: the lane-split decoder, its address table in global memory (registers) */
-    bool reg = false; /* ... or the register-resident decoder: no table */
     for (int i = 0; i != spec::NOF_SPECS; ++i) {
       if (spec::k_specs[i]->bg == g.bg && spec::k_specs[i]->Z == g.Z) {
         qid = spec::is_quad(*spec::k_specs[i]) ? i : -1;
-        reg = spec::is_reg(*spec::k_specs[i]);
       }
     }
-    if (reg) {
-      l.split_tab = 0;
-    } else if (qid >= 0) {
+    if (qid >= 0) {
       l.split_tab = static_cast<uint32_t>(quad_table_offset(qid));
     } else if (g.bg == 1) {
       const uint32_t waves = std::max<uint32_t>(2U * ((g.Z + 63U) / 64U), (g.Z + 31U) / 32U);
@@ -271,9 +267,6 @@ int spec_waves(int id)
   if (id < 0 || id >= spec::NOF_SPECS) {
     return 0;
   }
-  if (spec::is_reg(*spec::k_specs[id])) {
-    return 1; /* the register-resident decoder: one wave per codeblock */
-  }
   return spec::is_quad(*spec::k_specs[id]) ? spec::k_quads[id]->waves : spec::k_specs[id]->waves;
 }
 
@@ -352,7 +345,7 @@ int spec_unit(int id)
 bool spec_matches(const graph_desc& g, const lds_layout& lay, const spec::sgraph& k)
 {
   if (g.bg != k.bg || g.Z != k.Z || g.M != k.M || g.N_full != k.N_full || lay.soft != 0 ||
-      lay.soft_stride != static_cast<uint32_t>(spec::SOFT_COPIES * spec::SOFT_BYTES) * g.Z) {
+      lay.soft_stride != g.Z) {
     return false;
   }
   for (int m = 0; m < k.M; ++m) {

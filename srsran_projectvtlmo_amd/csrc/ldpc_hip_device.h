@@ -55,9 +55,9 @@ constexpr int DIAG_CB_WORDS  = 1024 * 8 * 2;
 /* The one-wave graphs' lane-split address tables (ldpc_spec.h qgraph, ldpc_decode_body.h sp::qdec), after the
  * diagnostic region: graph by graph at the offsets ldpc_graph.cpp quad_table_offset gives, slot q of lane tid at word
  * q * (waves * 64) + tid. Written once per context by ldpc_split_table_kernel, held in registers by each codeblock. */
-/* x^k mod G for k < CRC_XPOW_WORDS, per poly id p at CRC_XPOW_OFFSET + p * CRC_XPOW_WORDS: the register-resident
- * decoder's early-stop CRC (sp::rdec::et_setup), bit i of an L-bit message contributing x^(L - 1 - i + order) mod G;
- * K Z + order <= 22 * 64 + 24 for its graphs (Z <= 64). */
+/* x^k mod G for k < CRC_XPOW_WORDS, per poly id p at CRC_XPOW_OFFSET + p * CRC_XPOW_WORDS: written by the host
+ * (build_crc_tables) and read by no kernel since the register-resident one-wave decoder, whose early-stop CRC used
+ * it, was removed; the region stays because the offsets after it are kernel arguments. */
 constexpr int CRC_XPOW_OFFSET = DTAB_OFFSET + DTAB_WORDS + 1024 * 8 * 2;
 constexpr int CRC_XPOW_WORDS  = 1536;
 constexpr int QUAD_TAB_OFFSET = CRC_XPOW_OFFSET + 3 * CRC_XPOW_WORDS;
@@ -115,9 +115,9 @@ struct graph_desc {
 
 /* LDS carve-up for one decoder launch (every offset a multiple of 16; cdna_hip_programming.md G17). */
 struct lds_layout {
-  uint32_t soft;   /* soft bits, N_full columns of soft_stride bytes (int8; binary16 in the specialised kernels) */
-  uint32_t soft_stride; /* Z; specialised kernels: SOFT_BYTES Z (4 Z with ldpc_spec.h SOFT_COPIES = 4) */
-  uint32_t soft_read;   /* offset of the copy the decoder reads inside a column: 0; Z for the specialised kernel */
+  uint32_t soft;   /* soft bits, N_full columns of soft_stride bytes (int8) */
+  uint32_t soft_stride; /* bytes per column: always Z (one int8 copy per column in every kernel) */
+  uint32_t soft_read;   /* offset of the copy the decoder reads inside a column: always 0 */
   uint32_t c2v;    /* int8 c2v per edge, n_edges * Z        */
   uint32_t hard;   /* packed hard bits, ceil(K*Z/8) + 16    */
   uint32_t red;    /* uint32 reduction scratch, 32 words    */

@@ -39,78 +39,29 @@ constexpr int k_nof_edges = static_cast<int>(sizeof(k_edges) / sizeof(k_edges[0]
 constexpr int MAX_ROWS  = 46;
 constexpr int MAX_DEG   = 19;
 constexpr int MAX_STEPS = 48;
-#ifndef LDPC_SPEC_MAX_POS
-#define LDPC_SPEC_MAX_POS 12
-#endif
-constexpr int MAX_POS   = LDPC_SPEC_MAX_POS; /* positions (edge slots) per lane and step */
+constexpr int MAX_POS   = 12; /* positions (edge slots) per lane and step */
 
 /* A single-row step of this degree or more is split over lane pairs (P = 2). Splitting doubles the waves on the row
- * but costs a per-lane address select per edge and the partner merge; below degree 12 the unsplit row (6 waves, two
- * on the busiest SIMD) is faster (C2 batch: 163 us against 167 us with every single row of degree >= 6 split). */
-#ifndef LDPC_SPEC_SPLIT_MIN_DEGREE
-#define LDPC_SPEC_SPLIT_MIN_DEGREE 12
-#endif
-constexpr int SPLIT_MIN_DEGREE = LDPC_SPEC_SPLIT_MIN_DEGREE;
-/* Graphs with fewer waves per row (Z <= 320: at most 5) and BG2 (no row of degree 12) take their own thresholds;
- * splitting their single rows from degree 8, 6 or 4 was 1-12% slower on every graph (profiles/r02/split_variants.txt),
- * so none is split. */
-#ifndef LDPC_SPEC_SPLIT_SMALL
-#define LDPC_SPEC_SPLIT_SMALL 12
-#endif
-#ifndef LDPC_SPEC_SPLIT_BG2
-#define LDPC_SPEC_SPLIT_BG2 12
-#endif
-/* Graphs with one wave per row (Z <= 64) keep their single rows unsplit too: splitting from degree 4 or 6 was 1-12%
- * slower on every such graph (BG2 Z=36: 63.1 -> 71.0 / 66.0 us per 128-CB batch, profiles/r04/small_z_split_ab.txt):
- * at one wave per SIMD a step's time is its wave's instruction count, and the partner merge adds more than the
- * halved edge work removes. */
-constexpr int split_min_degree(int bg, int W)
-{
-  return W <= 5 ? LDPC_SPEC_SPLIT_SMALL : (bg == 2 ? LDPC_SPEC_SPLIT_BG2 : SPLIT_MIN_DEGREE);
-}
+ * but costs a per-lane address select per edge and the partner merge. One value for every graph; three measurements
+ * stand behind it:
+ *  - large BG1 graphs: below degree 12 the unsplit row (6 waves, two on the busiest SIMD) is faster (C2 batch: 163 us
+ *    against 167 us with every single row of degree >= 6 split);
+ *  - graphs with fewer waves per row (Z <= 320: at most 5) and BG2 (no row of degree 12): splitting their single rows
+ *    from degree 8, 6 or 4 was 1-12% slower on every graph (profiles/r02/split_variants.txt), so none is split;
+ *  - graphs with one wave per row (Z <= 64): splitting from degree 4 or 6 was 1-12% slower on every such graph (BG2
+ *    Z=36: 63.1 -> 71.0 / 66.0 us per 128-CB batch, profiles/r04/small_z_split_ab.txt): at one wave per SIMD a step's
+ *    time is its wave's instruction count, and the partner merge adds more than the halved edge work removes. */
+constexpr int SPLIT_MIN_DEGREE = 12;
 
 /* Precomputed addresses of BG1's split rows (0-3, degree 19: five address pairs per lane each): rows
- * [0, LDPC_SPEC_SPLIT_ADDR_ROWS) in registers, rows [LDPC_SPEC_SPLIT_ADDR_ROWS, LDPC_SPEC_SPLIT_LDS_ROWS) in an LDS
- * table (ldpc_decode_body.h, dec::fill_split), the rest computed in the step. */
-#ifndef LDPC_SPEC_SPLIT_ADDR_ROWS
-#define LDPC_SPEC_SPLIT_ADDR_ROWS 0
-#endif
+ * [0, LDPC_SPEC_SPLIT_LDS_ROWS) keep them in an LDS table, copied in each codeblock's prologue from the context's
+ * global copy (written once per context by ldpc_split_table_kernel, dec::write_split_table); the rest are computed in
+ * the step. The one tuning macro left: tools/fetch_sweep.sh builds the =0 variant (no table) to attribute HBM traffic. */
 #ifndef LDPC_SPEC_SPLIT_LDS_ROWS
 #define LDPC_SPEC_SPLIT_LDS_ROWS 4
 #endif
-/* 1: the LDS table is copied from the context's global copy (written once per context by ldpc_split_table_kernel) in
- * each codeblock's prologue; 0: computed by every codeblock (dec::fill_split) */
-#ifndef LDPC_SPEC_SPLIT_COPY
-#define LDPC_SPEC_SPLIT_COPY 1
-#endif
 /* LDS table size in address pairs per lane (a BG1 workgroup's waves x 64 lanes, 4 bytes each) */
-constexpr int SPLIT_LDS_PAIRS = LDPC_SPEC_SPLIT_LDS_ROWS > LDPC_SPEC_SPLIT_ADDR_ROWS
-                                    ? 5 * (LDPC_SPEC_SPLIT_LDS_ROWS - LDPC_SPEC_SPLIT_ADDR_ROWS) : 0;
-
-/* Soft-bit copies per column in LDS: 1 (one write per edge; the lane computes (t + shift) mod Z, three VALU
- * instructions) or 4 (reads and writes at t + shift without a modulo, three writes per edge). An LDS write costs
- * 4 cycles of the CU's LDS pipe whatever its width or active lanes (tools/ubench/lds3.hip, lds4.hip); on the C2 batch
- * one copy is 172 us, four copies 182 us (profiles/r02/variants.txt). */
-#ifndef LDPC_SPEC_SOFT_COPIES
-#define LDPC_SPEC_SOFT_COPIES 1
-#endif
-constexpr int SOFT_COPIES = LDPC_SPEC_SOFT_COPIES;
-static_assert(SOFT_COPIES == 1 || SOFT_COPIES == 4, "soft-bit copies");
-
-/* Soft-bit element of the specialised decoders, in LDS and in their registers: 1 = int8; 2 = IEEE binary16 holding
- * the same integers (exact: every value the decoder forms is an integer of magnitude below 2048). In binary16 a
- * value's sign and magnitude are separate bits, so |v2c|, the sign parity and every sign application of the
- * check-node update become full-rate bitwise VOP2 instructions (v_and / v_xor / v_or on both halves at once) instead
- * of half-rate packed ones (sp::pass1 / pass2: 474 fewer packed and 612 more full-rate instructions per BG1 Z=384
- * iteration, tools/step_isa.py), with ds_read_u16 / ds_write_b16 at even addresses. Bit-exact (tests/test_f16_arith.py
- * exhaustively, the whole -m gpu suite on the GPU), and no faster: C2 137.5 against 137.0 us, every other graph within
- * +-2% (profiles/r05/ab_f16_vs_i8.txt) -- as round 3's XOR-sign variant found, trading packed instructions for more
- * full-rate ones does not pay in this kernel. Off by default; -DLDPC_SPEC_F16=1 builds it. */
-#ifndef LDPC_SPEC_F16
-#define LDPC_SPEC_F16 0
-#endif
-constexpr int SOFT_BYTES = LDPC_SPEC_F16 ? 2 : 1;
-static_assert(SOFT_BYTES == 1 || SOFT_COPIES == 1, "binary16 soft bits: one copy per column");
+constexpr int SPLIT_LDS_PAIRS = 5 * LDPC_SPEC_SPLIT_LDS_ROWS;
 
 /* Extension edges in registers. Every row m >= 4 has one edge on its extension column (>= K + 4): degree 1, shift 0,
  * read and written by this row's own lane only. For such a column the reference's messages are trivial: v2c at the
@@ -120,15 +71,8 @@ static_assert(SOFT_BYTES == 1 || SOFT_COPIES == 1, "binary16 soft bits: one copy
  * its magnitude and sign in a register, and a sticky "went infinite" update per visit (dec::ext_update). Edges are
  * processed in pairs and a row of odd degree carries a dummy half, so taking the extension edge out of an odd-degree
  * row removes a whole pair (BG1: 26 of rows 4-45, 173 -> 147 pairs per check node and iteration); the state takes the
- * c2v slot the pair leaves. Even-degree rows would lose no pair and keep their extension edge in LDS.
- * ext_reg_graph gates the conversion per graph at compile time. */
-#ifndef LDPC_SPEC_EXT_REG
-#define LDPC_SPEC_EXT_REG 1
-#endif
-constexpr bool ext_reg_graph(int /* bg */, int /* W */)
-{
-  return LDPC_SPEC_EXT_REG != 0 && SOFT_BYTES == 1 && SOFT_COPIES == 1;
-}
+ * c2v slot the pair leaves. Even-degree rows would lose no pair and keep their extension edge in LDS. Every graph
+ * converts its odd rows (ext_reg_edge is where a per-graph gate would go). */
 
 struct srow {
   int deg = 0;
@@ -142,7 +86,7 @@ struct srow {
  * nearly: positions [0, nearly) (whole pairs) were read and passed through pass 1 in the previous step by the same
  * wave group (see sstep::e). q0: first c2v pair slot (slots q0 .. q0 + (npos + 1) / 2 - 1 of the group's lanes).
  * xe >= 0: the row's extension edge (column xcol) is not among the positions; its state is in slot q0 + npos / 2
- * (LDPC_SPEC_EXT_REG; npos is even then). */
+ * (ext_reg_edge; npos is even then). */
 struct srole {
   int row = -1, p = 1, npos = 0, grp = 0, nearly = 0, q0 = 0, xe = -1, xcol = -1;
   int e0[MAX_POS] = {};
@@ -155,9 +99,6 @@ struct srole {
  * order), keeping the partial minima, parity, v2c magnitudes, signs and addresses in registers across the barrier; in
  * the next step it reads the remaining (shared-column) edges, finishes pass 1 and updates the row. Every soft bit is
  * read after the last write to it in layer order, so the result is bit-identical to the serial schedule. */
-#ifndef LDPC_SPEC_PIPELINE
-#define LDPC_SPEC_PIPELINE 1
-#endif
 
 struct sstep {
   srole r[2]; /* r[1].row < 0 for a single-row step */
@@ -222,13 +163,12 @@ constexpr bool ext_columns_degree_one(const sgraph& g)
   return true;
 }
 
-/* The edge of an unsplit role (p == 1) of row r that is kept in a register instead of a position (LDPC_SPEC_EXT_REG):
- * the row's edge on a column >= K + 4 with shift 0, when that column has degree 1 in the whole graph and the row's
+/* The edge of an unsplit role (p == 1) of row r that is kept in a register instead of a position: the row's edge on a column >= K + 4 with shift 0, when that column has degree 1 in the whole graph and the row's
  * degree is odd; -1 otherwise. */
 constexpr int ext_reg_edge(const sgraph& g, int r, int p)
 {
   const srow& row = g.rows[r];
-  if (!ext_reg_graph(g.bg, g.W) || p != 1 || (row.deg & 1) == 0) {
+  if (p != 1 || (row.deg & 1) == 0) {
     return -1;
   }
   for (int k = 0; k < row.deg; ++k) {
@@ -293,7 +233,7 @@ constexpr sgraph make(int bg, int Z, int ils)
     sstep&     st   = g.steps[g.n_steps];
     st.r[0].row     = m;
     st.r[1].row     = pair ? m + 1 : -1;
-    st.r[0].p       = (!pair && g.rows[m].deg >= split_min_degree(bg, g.W)) ? 2 : 1;
+    st.r[0].p       = (!pair && g.rows[m].deg >= SPLIT_MIN_DEGREE) ? 2 : 1;
     ++g.n_steps;
     m += pair ? 2 : 1;
   }
@@ -314,7 +254,7 @@ constexpr sgraph make(int bg, int Z, int ils)
     }
   }
   /* early positions: the next single row's edges on columns this step's row does not write, first (whole pairs) */
-  for (int s = 0; LDPC_SPEC_PIPELINE && s + 1 < g.n_steps; ++s) {
+  for (int s = 0; s + 1 < g.n_steps; ++s) {
     if (!is_single_p1(g.steps[s]) || !is_single_p1(g.steps[s + 1])) {
       continue;
     }
@@ -446,117 +386,6 @@ constexpr bool roles_cover_edges(const sgraph& g)
   return true;
 }
 
-/* ---- Register-resident schedules of the one-wave graphs (Z <= 64) --------------------------------------------------
- * A Z <= 64 codeblock runs on ONE wave, one lane per check node, with every column's Z soft bits in a register (lane t
- * of column c's register: the soft bit of position (t + rho_c) mod Z, in one 16-bit half). Row r reads edge (c, s) as
- * the value at lane (t + s - rho_c) mod Z of that register (one ds_bpermute_b32, none when s == rho_c), and its
- * updated value for position (t + s) mod Z is computed by lane t: so the result register IS column c's register from
- * then on, with rho_c = s -- writes cost nothing, no LDS round trip, no barrier, and the whole iteration is one
- * straight-line instruction stream the compiler schedules across rows (the next row's reads of columns this row does
- * not write overlap its update). The layer order is still ldpc_decoder_impl.cpp:116-123's, one row after the other.
- *
- * Everything about the registers is compile-time: which column lives in which register half with which rotation at
- * every row (make_reg simulates the iteration), so each read is a constant rotation k = (s - rho_c) mod Z. The state at
- * the iteration boundary is the state after a full iteration (every column is written each iteration), and the
- * codeblock's registers are loaded from LDS in that state. Rows beyond the codeblock's layer count (impl.cpp:103-114)
- * are skipped in chunks: every LDPC_SPEC_REG_EXIT_EVERY rows a uniform branch leaves the iteration, re-rotating the
- * columns the skipped rows would have left elsewhere; rows in the last, partly active chunk run as the identity
- * (their c2v stays zero and their scaled magnitudes are forced to zero: v2c = soft, soft' = soft).
- *
- * Measured (round 5): bit-exact on every graph, and SLOWER than the lane-split decoder below on every one-wave graph
- * (128-CB batches, 8 it: BG2 Z=36 67 against 58 us, BG1 Z=36 120 against 71 us; profiles/r05/ab_reg_vs_quad_v1.txt,
- * ab_reg_nobarrier.txt). One iteration is 2,800 (BG2) to 4,300 (BG1) VALU instructions on ONE SIMD -- an issue floor
- * of 4.4-6.7 us per iteration before any stall -- and the row-to-row dependency chain stalls the lone wave for about
- * as long again (profiles/r05/reg_decoder_isa.txt); the LDS decoders spread the same work over 2-4 waves on
- * different SIMDs. Off by default; -DLDPC_SPEC_REG=1 builds it. */
-#ifndef LDPC_SPEC_REG
-#define LDPC_SPEC_REG 0
-#endif
-#ifndef LDPC_SPEC_REG_EXIT_EVERY
-#define LDPC_SPEC_REG_EXIT_EVERY 6
-#endif
-constexpr int REG_MAX_COLS  = 68;
-constexpr int REG_MAX_EXITS = 8;
-constexpr int REG_ROW_PAIRS = 10; /* register id of row r's pair i: r * REG_ROW_PAIRS + i */
-
-/* a column's register: lane t holds position (t + rho) mod Z in 16-bit half `half` of register `reg` */
-struct rcol {
-  int rho = 0, half = 0, reg = -1;
-};
-/* an edge of a row (pair i = edges 2i, 2i + 1): its column, read rotation k = (shift - rho) mod Z, and source state */
-struct redge {
-  int col = 0, k = 0, half = 0, reg = -1;
-};
-struct rrow {
-  int   deg = 0, q0 = 0; /* q0: first c2v pair register */
-  redge e[MAX_DEG] = {};
-};
-struct rgraph {
-  int   n_pairs = 0, n_exits = 0;
-  bool  valid = false;
-  rrow  rows[MAX_ROWS]      = {};
-  rcol  end[REG_MAX_COLS]   = {}; /* at the iteration boundary */
-  int   partner[REG_MAX_COLS] = {}; /* the other column of its boundary register, or -1 */
-  int   exit_row[REG_MAX_EXITS] = {};
-  rcol  at_exit[REG_MAX_EXITS][REG_MAX_COLS] = {}; /* before row exit_row[x] */
-};
-
-constexpr bool is_reg(const sgraph& g) { return LDPC_SPEC_REG != 0 && g.Z <= 64; }
-
-constexpr rgraph make_reg(const sgraph& g)
-{
-  rgraph R{};
-  if (!is_reg(g) || !g.valid || g.N_full > REG_MAX_COLS) {
-    return R;
-  }
-  rcol st[REG_MAX_COLS] = {};
-  for (int pass = 0; pass < 2; ++pass) { /* pass 0: the boundary state; pass 1: from it, every row's edges */
-    int q = 0;
-    for (int r = 0; r < g.M; ++r) {
-      const srow& row = g.rows[r];
-      if (pass == 1 && r >= LDPC_SPEC_REG_EXIT_EVERY && r % LDPC_SPEC_REG_EXIT_EVERY == 0 &&
-          R.n_exits < REG_MAX_EXITS) {
-        R.exit_row[R.n_exits] = r;
-        for (int c = 0; c < g.N_full; ++c) {
-          R.at_exit[R.n_exits][c] = st[c];
-        }
-        ++R.n_exits;
-      }
-      if (pass == 1) {
-        R.rows[r].deg = row.deg;
-        R.rows[r].q0  = q;
-        for (int e = 0; e < row.deg; ++e) {
-          const rcol& s  = st[row.col[e]];
-          R.rows[r].e[e] = redge{row.col[e], (row.sh[e] - s.rho + g.Z) % g.Z, s.half, s.reg};
-        }
-      }
-      q += (row.deg + 1) / 2;
-      for (int e = 0; e < row.deg; ++e) {
-        st[row.col[e]] = rcol{row.sh[e], e & 1, r * REG_ROW_PAIRS + e / 2};
-      }
-    }
-    if (pass == 0) {
-      for (int c = 0; c < g.N_full; ++c) {
-        R.end[c] = st[c];
-      }
-    } else {
-      R.n_pairs = q;
-    }
-  }
-  bool ok = true;
-  for (int c = 0; c < g.N_full; ++c) {
-    ok = ok && st[c].reg >= 0 && st[c].reg == R.end[c].reg && st[c].rho == R.end[c].rho && st[c].half == R.end[c].half;
-    R.partner[c] = -1;
-    for (int o = 0; o < g.N_full; ++o) {
-      if (o != c && R.end[o].reg == R.end[c].reg) {
-        R.partner[c] = o;
-      }
-    }
-  }
-  R.valid = ok;
-  return R;
-}
-
 /* ---- Lane-split schedules of the one-wave graphs (W == 1, Z <= 64) -------------------------------------------------
  * With one lane per check node a row of a Z <= 64 graph is one wave, whose instruction stream (every edge of the row
  * in turn: about 12 issue slots per edge, 14 per row) sets the step time at one wave per SIMD: the BG2 Z=36 batch spent
@@ -569,9 +398,6 @@ constexpr rgraph make_reg(const sgraph& g)
  * (sp::pass2), so the results are those of the layer-serial decoder bit for bit. A lane's edge k + P j of a row has a
  * per-lane column and shift, so its soft-bit addresses are precomputed once per context (two 16-bit LDS addresses per
  * register, written by ldpc_split_table_kernel) and held in registers with the c2v pairs: one of each per step. */
-#ifndef LDPC_SPEC_QUAD
-#define LDPC_SPEC_QUAD 1
-#endif
 constexpr int QUAD_MAX_SLOTS = 64;
 
 struct qrole {
@@ -589,8 +415,7 @@ struct qgraph {
   qstep steps[MAX_STEPS] = {};
 };
 
-/* the register-resident decoder (is_reg) takes precedence */
-constexpr bool is_quad(const sgraph& g) { return LDPC_SPEC_QUAD != 0 && g.W == 1 && !is_reg(g); }
+constexpr bool is_quad(const sgraph& g) { return g.W == 1; }
 
 constexpr qgraph make_quad(const sgraph& g)
 {
@@ -676,9 +501,7 @@ constexpr int NOF_CORE_SPECS = 10; /* ids [0, 10): bodies of the mixed kernel */
                     early_roles_match(k_spec##id) && ext_columns_degree_one(k_spec##id),                              \
                 "specialised schedule " #id);                                                                          \
   constexpr qgraph k_quad##id = make_quad(k_spec##id);                                                                 \
-  static_assert(!is_quad(k_spec##id) || k_quad##id.valid, "lane-split schedule " #id);                              \
-  constexpr rgraph k_reg##id = make_reg(k_spec##id);                                                                   \
-  static_assert(!is_reg(k_spec##id) || k_reg##id.valid, "register-resident schedule " #id);
+  static_assert(!is_quad(k_spec##id) || k_quad##id.valid, "lane-split schedule " #id);
 LDPC_SPEC_TU_GRAPHS(LDPC_SPEC_DEFINE)
 #undef LDPC_SPEC_DEFINE
 
@@ -705,7 +528,6 @@ struct spec_graph;
   struct spec_graph<id> {                                                                                              \
     static constexpr const sgraph& g = k_spec##id;                                                                     \
     static constexpr const qgraph& q = k_quad##id;                                                                     \
-    static constexpr const rgraph& r = k_reg##id;                                                                      \
   };
 LDPC_SPEC_TU_GRAPHS(LDPC_SPEC_SEL)
 #undef LDPC_SPEC_SEL

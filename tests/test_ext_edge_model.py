@@ -1,5 +1,5 @@
 """The message of a degree-1 extension column, as the specialised decoder keeps it in a register (ldpc_spec.h,
-LDPC_SPEC_EXT_REG; ldpc_decode_body.h, dec::ext_state / ext_seed / ext_update), against the oracle's LLR arithmetic.
+ext_reg_edge; ldpc_decode_body.h, dec::ext_state / ext_seed / ext_update), against the oracle's LLR arithmetic.
 
 An extension column (>= K + 4) has one edge, shift 0, and is read and written by its row's own lane only. Its v2c at
 the next visit is llr_sub(llr_promotion_sum(c2v', v2c), c2v'): the same v2c unless the promotion sum overflowed, and

@@ -1,5 +1,5 @@
 """GPU parity of the specialised multi-wave decoder (sp::dec) with the extension edges of its odd-degree rows kept in
-registers (ldpc_spec.h, LDPC_SPEC_EXT_REG): one codeblock per case through the C ABI against oracle.ldpc_decode on the
+registers (ldpc_spec.h, ext_reg_edge): one codeblock per case through the C ABI against oracle.ldpc_decode on the
 packed message, the CRC status and the iteration count.
 
 Graphs: the smallest ones that run sp::dec (BG1 and BG2 at Z = 72, two waves per row), two with a half-filled last
