@@ -2192,7 +2192,7 @@ __global__ void __launch_bounds__(decode_max_threads<SPEC_ID>()) ldpc_dwq_decode
 
 /* The split-row address table of specialised graph SPEC_ID into dst (dec::write_split_table), or for a one-wave graph
  * its lane-split decoder's address table (qdec::write_table): one workgroup of the decoder's width, launched once per
- * context (ldpc_hip_api.cpp write_split_tables). */
+ * context (ldpc_hip_kernels.hip write_split_tables). */
 template <int SPEC_ID>
 __global__ void __launch_bounds__(768) ldpc_split_table_kernel(uint32_t* __restrict__ dst)
 {

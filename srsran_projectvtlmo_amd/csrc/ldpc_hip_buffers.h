@@ -1,5 +1,5 @@
 /* Host-side buffers of the HIP library: device buffers and pinned (page-locked) host buffers that grow on demand.
- * Shared by the decode path (ldpc_hip_api.cpp) and the PDSCH encoder queue (ldpc_hip_enc_queue.cpp). */
+ * Shared by the decode path (ldpc_hip_ctx.h) and the PDSCH encoder queue (ldpc_hip_enc_queue.cpp). */
 #pragma once
 
 #include <hip/hip_runtime.h>

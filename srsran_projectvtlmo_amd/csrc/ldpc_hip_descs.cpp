@@ -1,0 +1,311 @@
+/* C-ABI descriptors into kernel work items (ldpc_hip_descs.h). */
+#include "ldpc_hip_descs.h"
+
+#include <algorithm>
+
+namespace ldpc_hip {
+
+/* the C ABI's struct layouts are part of the contract (tests/test_abi.py checks the same sizes from Python) */
+static_assert(sizeof(ldpc_hip_dec_desc) == 32, "ldpc_hip_dec_desc layout");
+static_assert(sizeof(ldpc_hip_dematch_desc) == 20, "ldpc_hip_dematch_desc layout");
+static_assert(sizeof(ldpc_hip_hw_config) == 44, "ldpc_hip_hw_config layout");
+static_assert(sizeof(ldpc_hip_cb_result) == 4, "ldpc_hip_cb_result layout");
+static_assert(sizeof(ldpc_hip_tb_desc) == 40, "ldpc_hip_tb_desc layout");
+static_assert(sizeof(ldpc_hip_tb_result) == 4, "ldpc_hip_tb_result layout");
+static_assert(sizeof(ldpc_hip_enc_desc) == 24, "ldpc_hip_enc_desc layout");
+static_assert(sizeof(ldpc_hip_rm_desc) == 32, "ldpc_hip_rm_desc layout");
+static_assert(sizeof(ldpc_hip_demod_desc) == 32, "ldpc_hip_demod_desc layout");
+
+namespace {
+
+/* ---- pseudo-random sequence generator, host side (ldpc_hip_device.h) ----
+ * x^(2^k) mod g for both registers, built at load by repeated squaring from x (the recurrences enter through the
+ * reduction x^31 = x^3 + 1 / x^3 + x^2 + x + 1). A jump by n bits is one polynomial jump per set bit of n. */
+struct prs_host_tables {
+  uint32_t pow2[2][64];
+  prs_host_tables()
+  {
+    for (int x = 0; x != 2; ++x) {
+      uint32_t p = 2;
+      for (int k = 0; k != 64; ++k) {
+        pow2[x][k] = p;
+        p          = prs_mulmod(p, p, x == 0 ? PRS_G1 : PRS_G2);
+      }
+    }
+  }
+};
+const prs_host_tables g_prs_host;
+
+template <bool X2>
+uint32_t prs_advance(uint32_t s, uint64_t n)
+{
+  for (int k = 0; n != 0; ++k, n >>= 1) {
+    if ((n & 1U) != 0U) {
+      s = prs_jump_poly<X2>(s, g_prs_host.pow2[X2 ? 1 : 0][k]);
+    }
+  }
+  return s;
+}
+
+/* K and the full codeword's columns of a base graph (build_graph's g.K, g.N_full) */
+unsigned bg_K(int bg) { return bg == 1 ? 22U : 10U; }
+unsigned bg_N_full(int bg) { return bg == 1 ? 68U : 52U; }
+
+} // namespace
+
+/* Nc = 1600 bits on from the initial registers, then offset (two jumps: 1600 + offset may not fit 64 bits) */
+ldpc_hip_prs_state prs_state_at(uint32_t c_init, uint64_t offset)
+{
+  ldpc_hip_prs_state st;
+  st.x1 = prs_advance<false>(prs_advance<false>(1U, PRS_NC), offset);
+  st.x2 = prs_advance<true>(prs_advance<true>(c_init & PRS_MASK, PRS_NC), offset);
+  return st;
+}
+
+int graph_slot(int bg, unsigned Z)
+{
+  int pos = lifting_position(Z);
+  if (pos < 0 || (bg != 1 && bg != 2)) {
+    return -1;
+  }
+  return (bg - 1) * 51 + pos;
+}
+
+const char* make_dec_cb(const ldpc_hip_dec_desc& s, dec_cb& out)
+{
+  if (graph_slot(s.base_graph, s.lifting_size) < 0) {
+    return "invalid base graph / lifting size";
+  }
+  const unsigned Z  = s.lifting_size;
+  const unsigned KZ = bg_K(s.base_graph) * Z;
+  if (s.max_iterations == 0) {
+    return "Max iterations must be different to 0";
+  }
+  if (s.llr_length > (bg_N_full(s.base_graph) - 2U) * Z || s.llr_length < KZ + 2U * Z) {
+    return "input length out of range [(K+2)Z, N_short Z]";
+  }
+  if (s.nof_filler_bits >= KZ) {
+    return "invalid number of filler bits";
+  }
+  const unsigned crc_mode = s.crc_mode & ~LDPC_HIP_CRC_MODE_FLAG_KEEP_PASSED;
+  if (crc_mode > LDPC_HIP_CRC_MODE_CHECK_AFTER) {
+    return "invalid CRC mode";
+  }
+  if (crc_mode != LDPC_HIP_CRC_MODE_NONE && (s.crc_poly < 0 || s.crc_poly > 2)) {
+    return "invalid CRC polynomial";
+  }
+  const float sf = dec_scaling(s);
+  if (!(sf > 0.0f && sf < 1.0f)) {
+    return "Scaling factor must be between 0 and 1 exclusively";
+  }
+  out                 = dec_cb{};
+  out.llr_offset      = s.llr_offset;
+  out.out_offset      = s.out_offset;
+  out.llr_length      = s.llr_length;
+  out.nof_filler_bits = s.nof_filler_bits;
+  out.max_iterations  = s.max_iterations;
+  out.crc_mode        = static_cast<uint8_t>(crc_mode);
+  out.keep_passed     = (s.crc_mode & LDPC_HIP_CRC_MODE_FLAG_KEEP_PASSED) != 0 ? 1 : 0;
+  out.crc_poly        = (crc_mode == LDPC_HIP_CRC_MODE_NONE) ? 0 : s.crc_poly;
+  out.scaling_factor  = sf;
+  return nullptr;
+}
+
+const char* make_dec_cbs(uint32_t n, const ldpc_hip_dec_desc* descs, std::vector<dec_cb>& cbs)
+{
+  std::vector<dec_cb> by_caller(n);
+  for (uint32_t i = 0; i != n; ++i) {
+    if (const char* why = make_dec_cb(descs[i], by_caller[i])) {
+      return why;
+    }
+    by_caller[i].result_index = i;
+  }
+  /* launch groups: one kernel launch per (BG, Z, default-scaling) class */
+  auto key_of = [&](const dec_cb& c) {
+    const ldpc_hip_dec_desc& s = descs[c.result_index];
+    return 2 * graph_slot(s.base_graph, s.lifting_size) + (c.scaling_factor == 0.8f ? 0 : 1);
+  };
+  std::stable_sort(by_caller.begin(), by_caller.end(),
+                   [&](const dec_cb& a, const dec_cb& b) { return key_of(a) < key_of(b); });
+  cbs.swap(by_caller);
+  return nullptr;
+}
+
+ldpc_hip_dec_desc make_dec_desc_from_hw(const ldpc_hip_hw_config& cfg, uint32_t N, uint64_t soft_off, uint64_t out_off)
+{
+  ldpc_hip_dec_desc x{};
+  x.base_graph      = cfg.base_graph;
+  x.max_iterations  = static_cast<uint8_t>(cfg.max_nof_ldpc_iterations);
+  x.crc_mode        = cfg.use_early_stop ? LDPC_HIP_CRC_MODE_EARLY_STOP : LDPC_HIP_CRC_MODE_CHECK_AFTER;
+  x.crc_poly        = static_cast<int8_t>(cfg.cb_crc_type);
+  x.lifting_size    = static_cast<uint16_t>(cfg.lifting_size);
+  x.nof_filler_bits = static_cast<uint16_t>(cfg.nof_filler_bits);
+  x.llr_length      = N;
+  x.scaling_factor  = 0.8f; /* pusch_decoder default (ldpc_decoder.h:50) */
+  x.llr_offset      = soft_off;
+  x.out_offset      = out_off;
+  return x;
+}
+
+const char* make_dematch_cb(const ldpc_hip_dematch_desc& s, const int8_t* llr, int8_t* soft,
+                            const ldpc_hip_demod_desc* demod, const float* sym_base, const float* nv_base,
+                            const ldpc_hip_scramble_desc* scr, const dec_cb* paired, dematch_cb& out)
+{
+  const unsigned Qm = s.modulation_order;
+  if (s.rv > 3 || !(Qm == 1 || Qm == 2 || Qm == 4 || Qm == 6 || Qm == 8) || s.rm_length % Qm != 0) {
+    return "invalid rv / modulation / rm_length";
+  }
+  if (s.Nref > MAX_CB_LEN || s.cb_length > MAX_CB_LEN) {
+    return "N_ref / cb_length too large";
+  }
+  unsigned Z = 0, K = 0;
+  if (s.cb_length % 66 == 0) {
+    Z = s.cb_length / 66;
+    K = 22;
+  } else if (s.cb_length % 50 == 0) {
+    Z = s.cb_length / 50;
+    K = 10;
+  } else {
+    return "LDPC rate dematching: invalid input length.";
+  }
+  if (lifting_index(Z) < 0) {
+    return "LDPC rate dematching: invalid input length.";
+  }
+  if (s.nof_filler_bits >= (K - 2) * Z) {
+    return "LDPC rate dematching: invalid number of filler bits.";
+  }
+  /* the fused dematcher writes cb_length soft bits at the decode descriptor's offset, inside the workgroup that then
+   * decodes them: a length or filler mismatch would write into a neighbour's buffer while it is being decoded */
+  if (paired != nullptr && (s.cb_length != paired->llr_length || s.nof_filler_bits != paired->nof_filler_bits)) {
+    return "dematch_decode_launch: dematch descriptor does not match its codeblock "
+           "(cb_length != llr_length or filler bits differ)";
+  }
+  out = dematch_cb{};
+  if (demod != nullptr) {
+    /* the symbols are demodulated into the dematcher's LDS staging, which holds DM_STAGE LLRs */
+    if (!valid_modulation(demod->modulation) || bits_per_symbol(demod->modulation) != Qm ||
+        static_cast<uint64_t>(demod->nof_symbols) * Qm != s.rm_length || s.rm_length > DM_STAGE) {
+      return paired != nullptr ? "dematch_decode_launch: symbols x bits per symbol must equal rm_length <= 32768"
+                               : "demod_dematch_launch: symbols x bits per symbol must equal rm_length <= 32768";
+    }
+    out.sym   = sym_base + 2 * demod->symbol_offset;
+    out.nv    = nv_base + demod->noise_offset;
+    out.demod = demod->modulation;
+  } else {
+    out.llr = llr;
+  }
+  out.soft             = soft;
+  out.cb_length        = s.cb_length;
+  out.rm_length        = s.rm_length;
+  out.Nref             = s.Nref;
+  out.nof_filler_bits  = s.nof_filler_bits;
+  out.modulation_order = s.modulation_order;
+  out.rv               = s.rv;
+  out.new_data         = s.new_data;
+  if (scr != nullptr && scr->enable != 0) {
+    if (s.rm_length > DM_STAGE) {
+      return "scrambled codeblock with rm_length above 32768 cannot be descrambled in the dematcher: descramble it "
+             "with ldpc_hip_descramble_launch first";
+    }
+    const ldpc_hip_prs_state st = prs_state_at(scr->c_init, scr->seq_offset);
+    out.scr_x1                  = st.x1;
+    out.scr_x2                  = st.x2;
+  }
+  return nullptr;
+}
+
+const char* tb_desc_reason(const ldpc_hip_tb_desc& d)
+{
+  const unsigned C = d.nof_cbs;
+  if (C == 0 || d.tbs == 0 || d.tbs % 8 != 0 || d.msg_stride < (d.cb_msg_bits + 7U) / 8U) {
+    return "tb_join: invalid sizes";
+  }
+  if (d.cb_crc_bits != 16 && d.cb_crc_bits != 24) {
+    return "tb_join: CRC length must be 16 or 24";
+  }
+  if (d.tbs / 8U > static_cast<uint32_t>(TBJ_CHUNK * TBJ_MAX_CHUNKS)) {
+    return "tb_join: transport block too large";
+  }
+  if (C == 1) {
+    if (d.tbs + d.cb_crc_bits + d.nof_filler_bits > d.cb_msg_bits) {
+      return "tb_join: TB larger than its codeblock";
+    }
+  } else {
+    const unsigned kd = d.cb_msg_bits - d.cb_crc_bits - d.nof_filler_bits;
+    if (d.cb_crc_bits != 24 || d.cb_crc_bits + d.nof_filler_bits >= d.cb_msg_bits || d.tbs <= (C - 1U) * kd ||
+        d.tbs - (C - 1U) * kd + 24U > kd) {
+      return "tb_join: segmentation inconsistent with the TB size";
+    }
+  }
+  return nullptr;
+}
+
+const char* make_enc_cb(const ldpc_hip_enc_desc& d, const uint32_t* ext, enc_cb& out)
+{
+  const int slot = graph_slot(d.base_graph, d.lifting_size);
+  if (slot < 0) {
+    return "encode_launch: invalid base graph / lifting size";
+  }
+  const uint32_t Z  = d.lifting_size;
+  const uint32_t KZ = bg_K(d.base_graph) * Z;
+  if (d.cw_length == 0 || d.cw_length > (bg_N_full(d.base_graph) - 2U) * Z) {
+    return "encode_launch: codeword length out of range";
+  }
+  const uint32_t bit_off = ext != nullptr ? ext[0] : 0U;
+  const uint32_t data    = ext != nullptr ? ext[1] : KZ;
+  const uint32_t crc_at  = ext != nullptr ? ext[2] : 0U;
+  if (bit_off > 7 || data > KZ || (crc_at != 0 && (crc_at + 24 > KZ || data > crc_at))) {
+    return "encode_launch: message bit range out of range";
+  }
+  out = enc_cb{d.msg_offset, d.cw_offset, d.cw_length, slot, bit_off, data, crc_at, 0};
+  return nullptr;
+}
+
+/* ldpc_rate_matcher_impl.cpp:36-160 */
+const char* make_rm_cb(const ldpc_hip_rm_desc& d, ratematch_cb& out)
+{
+  static const uint32_t sf_bg1[4] = {0, 17, 33, 56}, sf_bg2[4] = {0, 13, 25, 43}; /* ldpc_rate_matcher_impl.cpp:33-34 */
+  const unsigned        N         = d.cb_length;
+  const bool            bg1       = (N % 66U) == 0;
+  if (!bg1 && (N % 50U) != 0) {
+    return "rate_match_launch: invalid codeblock length";
+  }
+  const unsigned Z = bg1 ? N / 66U : N / 50U;
+  if (graph_slot(bg1 ? 1 : 2, Z) < 0 || d.rv > 3 || d.modulation_order == 0 || d.modulation_order > 8 ||
+      d.rm_length == 0 || d.rm_length % d.modulation_order != 0) {
+    return "rate_match_launch: invalid parameters";
+  }
+  const unsigned nsys = ((bg1 ? 22U : 10U) - 2U) * Z;
+  if (d.nof_filler_bits >= nsys) {
+    return "rate_match_launch: invalid number of filler bits";
+  }
+  const unsigned Ncb = (d.Nref > 0) ? std::min<unsigned>(d.Nref, N) : N;
+  const uint64_t sf  = bg1 ? sf_bg1[d.rv] : sf_bg2[d.rv];
+  out                = ratematch_cb{};
+  out.cw_offset      = d.cw_offset;
+  out.out_offset     = d.out_offset;
+  out.cb_length      = N;
+  out.rm_length      = d.rm_length;
+  out.Ncb            = Ncb;
+  out.k0             = static_cast<uint32_t>((sf * Ncb) / N) * Z; /* :88-89, floor of an exact ratio */
+  out.fill_lo        = nsys - d.nof_filler_bits;
+  out.fill_hi        = nsys;
+  out.Qm             = d.modulation_order;
+  return nullptr;
+}
+
+const char* make_pdsch_cb(const ldpc_hip_enc_desc& ed, const uint32_t* ext, const ldpc_hip_rm_desc& rd,
+                          pdsch_enc_cb& out)
+{
+  const char* why = make_enc_cb(ed, ext, out.enc);
+  if (why == nullptr) {
+    why = make_rm_cb(rd, out.rm);
+  }
+  if (why == nullptr && (out.enc.cw_length != out.rm.cb_length ||
+                         out.enc.graph_slot != graph_slot(rd.cb_length % 66U == 0 ? 1 : 2, ed.lifting_size))) {
+    why = "pdsch_encode: encoder and rate matcher descriptors disagree";
+  }
+  return why;
+}
+
+} // namespace ldpc_hip

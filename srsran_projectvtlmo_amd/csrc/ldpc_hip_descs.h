@@ -1,0 +1,62 @@
+/*
+ * The one translation of each C-ABI descriptor (include/srsran_ldpc_hip.h) into the work item the kernels read
+ * (ldpc_hip_device.h), with its validation. Host only: no HIP runtime call, no context. Each make_* returns the reason
+ * its descriptor is invalid, or nullptr after filling the work item; the entry points report the reason through
+ * ldpc_hip_last_error with LDPC_HIP_EINVAL.
+ */
+#pragma once
+
+#include <cstdint>
+#include <vector>
+
+#include "ldpc_graph.h"
+
+namespace ldpc_hip {
+
+constexpr uint32_t MAX_CB_LEN = 66U * 384U; /* MAX_CODEBLOCK_SIZE (ldpc.h:113) */
+
+constexpr uint64_t align16(uint64_t x) { return (x + 15U) & ~static_cast<uint64_t>(15U); }
+
+inline bool     valid_modulation(int m) { return m == 0 || m == 1 || m == 2 || m == 4 || m == 6 || m == 8; }
+inline unsigned bits_per_symbol(int m) { return (m == 0 || m == 1) ? 1U : static_cast<unsigned>(m); }
+inline unsigned msg_bytes_of(int bg, unsigned Z) { return ((bg == 1 ? 22U : 10U) * Z + 7U) / 8U; }
+
+/* the wide schedule's graph slot of (bg, Z): BG1 then BG2, by lifting position; -1 for an invalid pair */
+int graph_slot(int bg, unsigned Z);
+
+/* the generator's state `offset` bits into the sequence of c_init (ldpc_hip_prs_init) */
+ldpc_hip_prs_state prs_state_at(uint32_t c_init, uint64_t offset);
+
+/* the scaling factor a decode descriptor asks for: 0 is the default, 0.8 (ldpc_decoder.h:50) */
+inline float dec_scaling(const ldpc_hip_dec_desc& d) { return d.scaling_factor == 0.0f ? 0.8f : d.scaling_factor; }
+
+/* ---- decoder ---- */
+/* one decode work item (result_index 0) */
+const char* make_dec_cb(const ldpc_hip_dec_desc& s, dec_cb& out);
+/* A plan's work items in launch order: every descriptor validated, then grouped by (BG, Z, default scaling or not)
+ * with the caller's order kept inside a group; cbs[i].result_index is the caller's index of block i. */
+const char* make_dec_cbs(uint32_t n, const ldpc_hip_dec_desc* descs, std::vector<dec_cb>& cbs);
+/* the decode a HAL operation configures (hw_accelerator_pusch_dec::configure_operation): N soft bits at soft_off, the
+ * message at out_off, early stop or a CRC check after the last iteration, the default scaling factor */
+ldpc_hip_dec_desc make_dec_desc_from_hw(const ldpc_hip_hw_config& cfg, uint32_t N, uint64_t soft_off, uint64_t out_off);
+
+/* ---- rate dematcher ---- */
+/* One dematch work item reading llr (or, with demod, soft-demodulating its symbols from sym_base / nv_base) and
+ * combining into soft; scr (may be null, or disabled) descrambles in the dematcher. paired: the decode work item whose
+ * workgroup runs this dematcher first (the fused launch), which must agree in length and filler bits; it also names
+ * the entry point in the demodulator's rejection. Pointers may be null and set later. */
+const char* make_dematch_cb(const ldpc_hip_dematch_desc& s, const int8_t* llr, int8_t* soft,
+                            const ldpc_hip_demod_desc* demod, const float* sym_base, const float* nv_base,
+                            const ldpc_hip_scramble_desc* scr, const dec_cb* paired, dematch_cb& out);
+
+/* ---- transport-block join ---- */
+const char* tb_desc_reason(const ldpc_hip_tb_desc& d);
+
+/* ---- encoder, rate matcher, the PDSCH queue's fused pair ---- */
+/* ext: message bit offset (< 8), data bits (<= K Z) and CRC24B position (0: none); nullptr: K Z bits from bit 0 */
+const char* make_enc_cb(const ldpc_hip_enc_desc& d, const uint32_t* ext, enc_cb& out);
+const char* make_rm_cb(const ldpc_hip_rm_desc& d, ratematch_cb& out);
+const char* make_pdsch_cb(const ldpc_hip_enc_desc& ed, const uint32_t* ext, const ldpc_hip_rm_desc& rd,
+                          pdsch_enc_cb& out);
+
+} // namespace ldpc_hip

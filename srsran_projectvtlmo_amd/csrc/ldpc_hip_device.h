@@ -1,5 +1,5 @@
 /*
- * Device-side data layouts shared by the host runtime (ldpc_hip_api.cpp) and the gfx950 kernels
+ * Device-side data layouts shared by the host runtime (ldpc_hip_descs.cpp fills them) and the gfx950 kernels
  * (ldpc_hip_kernels.hip). Plain structs only; the C ABI in include/srsran_ldpc_hip.h never exposes them.
  */
 #pragma once

@@ -16,7 +16,7 @@
  *           the ticket not done, the ticket is unclaimed and a new grid is launched.
  */
 #include "ldpc_hip_dwq.h"
-#include "ldpc_graph.h"
+#include "ldpc_hip_launch.h"
 
 #include <algorithm>
 #include <atomic>
@@ -34,38 +34,14 @@
 
 namespace ldpc_hip {
 
-const void* dwq_kernel_dematch();
-const void* dwq_kernel_encode();
-const void* dwq_kernel_copy();
-#define LDPC_DWQ_UNIT_DECL(u) const void* dwq_kernel_##u(int id);
-LDPC_DWQ_UNIT_DECL(core)
-LDPC_DWQ_UNIT_DECL(a)
-LDPC_DWQ_UNIT_DECL(b)
-LDPC_DWQ_UNIT_DECL(c)
-LDPC_DWQ_UNIT_DECL(d)
-LDPC_DWQ_UNIT_DECL(e)
-LDPC_DWQ_UNIT_DECL(f)
-LDPC_DWQ_UNIT_DECL(g)
-LDPC_DWQ_UNIT_DECL(h)
-LDPC_DWQ_UNIT_DECL(i)
-LDPC_DWQ_UNIT_DECL(j)
-LDPC_DWQ_UNIT_DECL(k)
-LDPC_DWQ_UNIT_DECL(l)
-LDPC_DWQ_UNIT_DECL(m)
-LDPC_DWQ_UNIT_DECL(n)
-LDPC_DWQ_UNIT_DECL(o)
-LDPC_DWQ_UNIT_DECL(p)
-#undef LDPC_DWQ_UNIT_DECL
-
 namespace {
 
 /* the persistent kernel of a queue key: 0 dematch-only items, 1 + id the specialised graph id (found in its unit) */
 const void* key_kernel(int key)
 {
-  static const void* (*const k[])(int) = {dwq_kernel_core, dwq_kernel_a, dwq_kernel_b, dwq_kernel_c, dwq_kernel_d,
-                                          dwq_kernel_e,    dwq_kernel_f, dwq_kernel_g, dwq_kernel_h, dwq_kernel_i,
-                                          dwq_kernel_j,    dwq_kernel_k, dwq_kernel_l, dwq_kernel_m, dwq_kernel_n,
-                                          dwq_kernel_o,    dwq_kernel_p};
+#define LDPC_DWQ_UNIT_PTR(u) dwq_kernel_##u,
+  static const void* (*const k[])(int) = {LDPC_KERNEL_UNITS(LDPC_DWQ_UNIT_PTR)};
+#undef LDPC_DWQ_UNIT_PTR
   if (key == 0) {
     return dwq_kernel_dematch();
   }

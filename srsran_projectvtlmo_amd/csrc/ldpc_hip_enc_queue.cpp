@@ -19,47 +19,15 @@
 #include <new>
 #include <vector>
 
-#include "ldpc_hip_buffers.h"
-#include "srsran_ldpc_hip.h"
+#include "ldpc_hip_ctx.h"
+#include "ldpc_hip_launch.h"
 
 using namespace ldpc_hip;
-
-namespace ldpc_hip {
-uint32_t    ctx_launch_flags(const ldpc_hip_ctx* ctx); /* ldpc_hip_api.cpp */
-hipStream_t ctx_hal_stream(const ldpc_hip_ctx* ctx);   /* the HAL queue's current stream (ldpc_hip_api.cpp) */
-size_t pdsch_enc_desc_bytes(); /* ldpc_hip_api.cpp */
-int    pdsch_encode_submit(ldpc_hip_ctx* ctx, uint32_t n, const ldpc_hip_enc_desc* ed, const uint32_t* ext,
-                           const ldpc_hip_rm_desc* rd, const uint8_t* d_msgs, uint8_t* d_out, void** qo,
-                           uint32_t* tickets);
-bool   pdsch_encode_done(void* q, uint32_t ticket);
-int    pdsch_encode_wait(void* q, uint32_t ticket);
-int    pdsch_encode_launch(ldpc_hip_ctx* ctx, uint32_t n, const ldpc_hip_enc_desc* ed, const uint32_t* ext,
-                           const ldpc_hip_rm_desc* rd, const uint8_t* d_msgs, uint8_t* d_out, void* h_desc,
-                           const void* d_desc, void* stream);
-} // namespace ldpc_hip
 
 namespace {
 
 constexpr uint32_t MAX_NOF_SEGMENTS = 162;    /* sch_constants.h:38 */
 constexpr uint32_t MAX_TB_BYTES     = 159749; /* the largest NR TBS (1,277,992 bits) in bytes */
-
-uint64_t align16(uint64_t x) { return (x + 15U) & ~static_cast<uint64_t>(15U); }
-
-bool valid_lifting_size(uint32_t z)
-{
-  static const uint32_t a_set[8] = {2, 3, 5, 7, 9, 11, 13, 15};
-  for (uint32_t a : a_set) {
-    for (uint32_t v = a; v <= 384; v *= 2) {
-      if (v == z) {
-        return true;
-      }
-    }
-  }
-  return false;
-}
-
-uint32_t bits_per_symbol(uint8_t m) { return (m == 0 || m == 1) ? 1U : m; }
-bool     valid_modulation(uint8_t m) { return m == 0 || m == 1 || m == 2 || m == 4 || m == 6 || m == 8; }
 
 /* byte -> its eight bits, MSB first, one per byte (little-endian uint64 image) */
 struct unpack_table {
@@ -139,6 +107,37 @@ struct enc_op {
 
 enum class enc_state { idle, staging, launched };
 
+constexpr uint32_t NO_TICKET = 0xffffffffU; /* an item that was not published */
+
+/* A small batch as items of the encoder's work queue (ldpc_hip_dwq.h DWQ_KEY_ENC; ldpc_dwq_encode_kernel) instead of a
+ * launch: one item per codeblock, tickets[i] its ticket. Returns LDPC_HIP_OK with *qo set, 1 when the queue cannot
+ * serve the batch now (nothing published: launch instead), or an error after which the published items must still be
+ * waited for. */
+int pdsch_encode_submit(ldpc_hip_ctx* ctx, const std::vector<pdsch_enc_cb>& c, const uint8_t* d_msgs, uint8_t* d_out,
+                        dwq** qo, std::vector<uint32_t>& tickets)
+{
+  *qo = nullptr;
+  tickets.assign(c.size(), NO_TICKET);
+  dwq* q = ctx->use_dwq ? dwq_get(ctx->device, DWQ_KEY_ENC, ENC_THREADS, 0) : nullptr;
+  if (q == nullptr || !dwq_admit(q)) {
+    return 1;
+  }
+  *qo = q;
+  for (size_t i = 0; i != c.size(); ++i) {
+    const dwq_enc_payload pl{c[i], d_msgs, d_out, ctx->d_crc.as<uint32_t>()};
+    dwq_item              it{};
+    std::memcpy(static_cast<void*>(&it), &pl, sizeof(pl));
+    it.spec            = 1;
+    const hipError_t e = dwq_submit(q, it, tickets[i], false);
+    if (e != hipSuccess) {
+      dwq_unpin(q);
+      return ctx->hip_fail(e, "PDSCH work queue submit");
+    }
+  }
+  dwq_unpin(q);
+  return LDPC_HIP_OK;
+}
+
 } // namespace
 
 struct ldpc_hip_enc_queue {
@@ -157,7 +156,7 @@ struct ldpc_hip_enc_queue {
   enc_state                           state     = enc_state::idle;
   uint64_t                            msg_used = 0, out_used = 0;
   pinned_buffer                       h_msg, h_out, h_desc;
-  void*                               wq = nullptr; /* the batch went through the encoder's work queue      */
+  dwq*                                wq = nullptr; /* the batch went through the encoder's work queue      */
   std::vector<uint32_t>               tickets;      /* its items' tickets (0xffffffff: not published)      */
   bool                                complete = false;
   dev_buffer                          d_msg, d_out;
@@ -185,7 +184,9 @@ struct ldpc_hip_enc_queue {
   {
     if (wq != nullptr) { /* every published item, also after a failed submit */
       for (uint32_t t : tickets) {
-        (void)ldpc_hip::pdsch_encode_wait(wq, t);
+        if (t != NO_TICKET) {
+          (void)dwq_wait(wq, t);
+        }
       }
       complete = true;
     } else if (state == enc_state::launched) {
@@ -196,7 +197,7 @@ struct ldpc_hip_enc_queue {
    * LDS; one codeblock's descriptor goes by value, more are read in place from the pinned h_desc, so no descriptor
    * upload precedes the kernel). For a zero-copy batch (at most ENC_ZERO_COPY_MAX_BYTES staged and produced) the
    * kernel reads the messages straight from the pinned staging buffer and writes straight into the pinned output
-   * buffer (mapped host memory; the HAL decoder queue does the same, ldpc_hip_api.cpp hal_launch); otherwise one H2D
+   * buffer (mapped host memory; the HAL decoder queue does the same, ldpc_hip_hal.cpp hal_launch); otherwise one H2D
    * of the messages and one D2H of the packed outputs around it. */
   static constexpr uint64_t ENC_ZERO_COPY_MAX_BYTES = 1024U * 1024U;
   int launch()
@@ -214,28 +215,25 @@ struct ldpc_hip_enc_queue {
     (void)hipSetDevice(device);
     if (d_msg.reserve(msg_used) != hipSuccess || d_out.reserve(out_used) != hipSuccess ||
         h_out.reserve(out_used, 0) != hipSuccess ||
-        h_desc.reserve(units.size() * ldpc_hip::pdsch_enc_desc_bytes(), 0) != hipSuccess) {
+        h_desc.reserve(units.size() * sizeof(pdsch_enc_cb), 0) != hipSuccess) {
       return LDPC_HIP_EDEVICE;
     }
-    std::vector<ldpc_hip_enc_desc> ed(units.size());
-    std::vector<ldpc_hip_rm_desc>  rd(units.size());
-    std::vector<uint32_t>          ext(3 * units.size());
+    std::vector<pdsch_enc_cb> c(units.size()); /* the rate matcher's cw_offset is unused: the codeword stays in LDS */
     for (size_t i = 0; i != units.size(); ++i) {
-      const enc_unit& u = units[i];
-      ed[i]             = ldpc_hip_enc_desc{u.msg_off, 0, u.N, u.Z, u.bg, 0};
-      ext[3 * i]        = u.bit_off;
-      ext[3 * i + 1]    = u.data_bits;
-      ext[3 * i + 2]    = u.crc_at;
-      rd[i]             = ldpc_hip_rm_desc{0, u.out_off, u.N, u.E, u.Nref, static_cast<uint16_t>(u.F), u.Qm, u.rv};
+      const enc_unit&         u = units[i];
+      const ldpc_hip_enc_desc ed{u.msg_off, 0, u.N, u.Z, u.bg, 0};
+      const uint32_t          ext[3] = {u.bit_off, u.data_bits, u.crc_at};
+      const ldpc_hip_rm_desc  rd{0, u.out_off, u.N, u.E, u.Nref, static_cast<uint16_t>(u.F), u.Qm, u.rv};
+      if (const char* why = make_pdsch_cb(ed, ext, rd, c[i])) {
+        return ctx->fail(LDPC_HIP_EINVAL, why);
+      }
     }
     const bool zc = msg_used + out_used <= ENC_ZERO_COPY_MAX_BYTES && h_msg.dev != nullptr && h_out.dev != nullptr &&
-                    (ldpc_hip::ctx_launch_flags(ctx) & LDPC_HIP_LAUNCH_HAL_COPY) == 0;
+                    (ctx->params.launch_flags & LDPC_HIP_LAUNCH_HAL_COPY) == 0;
     uint8_t* const msg = zc ? h_msg.dev_as<uint8_t>() : d_msg.as<uint8_t>();
     uint8_t* const out = zc ? h_out.dev_as<uint8_t>() : d_out.as<uint8_t>();
     if (zc && units.size() <= ENC_DWQ_MAX_CBS) {
-      tickets.assign(units.size(), 0xffffffffU);
-      const int w = ldpc_hip::pdsch_encode_submit(ctx, static_cast<uint32_t>(units.size()), ed.data(), ext.data(),
-                                                  rd.data(), msg, out, &wq, tickets.data());
+      const int w = pdsch_encode_submit(ctx, c, msg, out, &wq, tickets);
       if (w == LDPC_HIP_OK) {
         state = enc_state::launched;
         return LDPC_HIP_OK;
@@ -249,10 +247,17 @@ struct ldpc_hip_enc_queue {
     if (!zc && hipMemcpyAsync(d_msg.ptr, h_msg.ptr, msg_used, hipMemcpyHostToDevice, stream) != hipSuccess) {
       return LDPC_HIP_EDEVICE;
     }
-    const int r = ldpc_hip::pdsch_encode_launch(ctx, static_cast<uint32_t>(units.size()), ed.data(), ext.data(),
-                                                rd.data(), msg, out, h_desc.ptr, h_desc.dev, stream);
-    if (r != LDPC_HIP_OK) {
-      return r;
+    if (c.size() > 1) {
+      if (h_desc.dev == nullptr) {
+        return LDPC_HIP_EINVAL;
+      }
+      std::memcpy(h_desc.ptr, c.data(), c.size() * sizeof(pdsch_enc_cb));
+    }
+    const hipError_t er = launch_pdsch_encode(h_desc.dev_as<pdsch_enc_cb>(), c.size() == 1 ? c.data() : nullptr,
+                                              static_cast<uint32_t>(c.size()), msg, out, ctx->d_crc.as<uint32_t>(),
+                                              abi_stream(ctx->stream, stream));
+    if (er != hipSuccess) {
+      return ctx->hip_fail(er, "ldpc_pdsch_encode_kernel launch");
     }
     if ((!zc && hipMemcpyAsync(h_out.ptr, d_out.ptr, out_used, hipMemcpyDeviceToHost, stream) != hipSuccess) ||
         hipEventRecord(done, stream) != hipSuccess) {
@@ -349,7 +354,7 @@ int ldpc_hip_enc_reserve(ldpc_hip_enc_queue* q)
   if (r != LDPC_HIP_OK) {
     return r;
   }
-  q->stream = ldpc_hip::ctx_hal_stream(q->ctx);
+  q->stream = q->ctx->hq_stream;
   return LDPC_HIP_OK;
 }
 
@@ -361,7 +366,7 @@ int ldpc_hip_enc_free(ldpc_hip_enc_queue* q)
   q->sync();
   q->reset(enc_state::idle);
   const int r = ldpc_hip_queue_free(q->ctx);
-  q->stream   = ldpc_hip::ctx_hal_stream(q->ctx);
+  q->stream   = q->ctx->hq_stream;
   return r;
 }
 
@@ -374,7 +379,7 @@ int ldpc_hip_enc_configure(ldpc_hip_enc_queue* q, uint32_t cb_index, const ldpc_
   const uint32_t                Qm = bits_per_symbol(c.modulation);
   /* cb_index: a segment index (CB mode) or 0 (TB mode); bounded so that a stray index cannot grow the tables */
   if (cb_index >= 4U * MAX_NOF_SEGMENTS || (c.base_graph != 1 && c.base_graph != 2) ||
-      !valid_lifting_size(c.lifting_size) || !valid_modulation(c.modulation) || c.rv > 3 || c.nof_segments == 0 ||
+      lifting_position(c.lifting_size) < 0 || !valid_modulation(c.modulation) || c.rv > 3 || c.nof_segments == 0 ||
       c.nof_segments > MAX_NOF_SEGMENTS) {
     return LDPC_HIP_EINVAL;
   }
@@ -499,7 +504,7 @@ int ldpc_hip_enc_dequeue(ldpc_hip_enc_queue* q, uint32_t segment_index, uint8_t*
   if (!q->complete) {
     if (q->wq != nullptr) { /* every item of the batch done (the work queue's done flags, no runtime call) */
       for (uint32_t t : q->tickets) {
-        if (!ldpc_hip::pdsch_encode_done(q->wq, t)) {
+        if (t != NO_TICKET && !dwq_done(q->wq, t)) {
           return LDPC_HIP_NOT_READY;
         }
       }

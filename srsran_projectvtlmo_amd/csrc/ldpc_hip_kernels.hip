@@ -8,6 +8,7 @@
 
 #define LDPC_SPEC_TU_GRAPHS LDPC_SPEC_GRAPHS_CORE
 #include "ldpc_decode_body.h"
+#include "ldpc_hip_launch.h"
 
 namespace ldpc_hip {
 
@@ -753,7 +754,7 @@ __global__ void __launch_bounds__(ENC_THREADS) ldpc_dwq_encode_kernel(dwq_args a
 }
 const void* dwq_kernel_encode() { return reinterpret_cast<const void*>(&ldpc_dwq_encode_kernel); }
 
-/* The HAL decoder's early copy (ldpc_hip_api.cpp hal_copy_staged): each item moves one piece of a large batch's staged
+/* The HAL decoder's early copy (ldpc_hip_hal.cpp hal_copy_staged): each item moves one piece of a large batch's staged
  * LLRs from pinned host memory into HBM while the caller is still enqueueing, COPY_UNROLL 16-byte loads per thread in
  * flight before any store (one PCIe round trip per 64 KiB per workgroup), so the batch kernel reads HBM. */
 __global__ void __launch_bounds__(COPY_THREADS) ldpc_dwq_copy_kernel(dwq_args a)
@@ -818,29 +819,7 @@ __global__ void __launch_bounds__(256) ldpc_rate_match_kernel(const ratematch_cb
   }
 }
 
-/* ---- host-side launch helpers (called from ldpc_hip_api.cpp) ---- */
-
-/* the specialised kernels instantiated in ldpc_spec_kernels_*.hip (their host launch stubs) */
-#define LDPC_SPEC_KERNEL_DECL(id, bg, z, ils) const void* spec_kernel_##id(); const void* spec_split_kernel_##id();
-LDPC_SPEC_GRAPHS_MID_A(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_MID_B(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_MID_C(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_MID_D(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_MID_E(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_MID_F(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_MID_G(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_MID_H(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_SMALL_I(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_SMALL_J(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_SMALL_K(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_SMALL_L(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_SMALL_M(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_SMALL_N(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_SMALL_O(LDPC_SPEC_KERNEL_DECL)
-LDPC_SPEC_GRAPHS_SMALL_P(LDPC_SPEC_KERNEL_DECL)
-#undef LDPC_SPEC_KERNEL_DECL
-int spec_waves(int id); /* ldpc_graph.cpp */
-long quad_table_offset(int id);
+/* ---- host-side launch helpers (ldpc_hip_launch.h) ---- */
 
 /* host launch stub of specialised kernel `id` (core: this unit; mid: ldpc_spec_kernels_*.hip) */
 const void* spec_kernel_ptr(int id)
@@ -848,11 +827,7 @@ const void* spec_kernel_ptr(int id)
 #define LDPC_SPEC_KERNEL(id, bg, z, ils) reinterpret_cast<const void*>(&ldpc_decode_kernel<true, id>),
 #define LDPC_SPEC_KERNEL_EXT(id, bg, z, ils) spec_kernel_##id(),
   static const void* const spec_kernels[] = {
-      LDPC_SPEC_GRAPHS_CORE(LDPC_SPEC_KERNEL) LDPC_SPEC_GRAPHS_MID_A(LDPC_SPEC_KERNEL_EXT)
-          LDPC_SPEC_GRAPHS_MID_B(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_MID_C(LDPC_SPEC_KERNEL_EXT)
-              LDPC_SPEC_GRAPHS_MID_D(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_MID_E(LDPC_SPEC_KERNEL_EXT)
-                  LDPC_SPEC_GRAPHS_MID_F(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_MID_G(LDPC_SPEC_KERNEL_EXT)
-                      LDPC_SPEC_GRAPHS_MID_H(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_I(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_J(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_K(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_L(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_M(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_N(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_O(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_P(LDPC_SPEC_KERNEL_EXT)};
+      LDPC_SPEC_GRAPHS_CORE(LDPC_SPEC_KERNEL) LDPC_SPEC_GRAPHS_UNITS(LDPC_SPEC_KERNEL_EXT)};
 #undef LDPC_SPEC_KERNEL
 #undef LDPC_SPEC_KERNEL_EXT
   static_assert(sizeof(spec_kernels) / sizeof(spec_kernels[0]) == spec::NOF_SPECS, "specialised kernel table");
@@ -865,11 +840,7 @@ const void* spec_split_kernel_ptr(int id)
 #define LDPC_SPEC_KERNEL(id, bg, z, ils) reinterpret_cast<const void*>(&ldpc_split_table_kernel<id>),
 #define LDPC_SPEC_KERNEL_EXT(id, bg, z, ils) spec_split_kernel_##id(),
   static const void* const split_kernels[] = {
-      LDPC_SPEC_GRAPHS_CORE(LDPC_SPEC_KERNEL) LDPC_SPEC_GRAPHS_MID_A(LDPC_SPEC_KERNEL_EXT)
-          LDPC_SPEC_GRAPHS_MID_B(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_MID_C(LDPC_SPEC_KERNEL_EXT)
-              LDPC_SPEC_GRAPHS_MID_D(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_MID_E(LDPC_SPEC_KERNEL_EXT)
-                  LDPC_SPEC_GRAPHS_MID_F(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_MID_G(LDPC_SPEC_KERNEL_EXT)
-                      LDPC_SPEC_GRAPHS_MID_H(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_I(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_J(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_K(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_L(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_M(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_N(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_O(LDPC_SPEC_KERNEL_EXT) LDPC_SPEC_GRAPHS_SMALL_P(LDPC_SPEC_KERNEL_EXT)};
+      LDPC_SPEC_GRAPHS_CORE(LDPC_SPEC_KERNEL) LDPC_SPEC_GRAPHS_UNITS(LDPC_SPEC_KERNEL_EXT)};
 #undef LDPC_SPEC_KERNEL
 #undef LDPC_SPEC_KERNEL_EXT
   static_assert(sizeof(split_kernels) / sizeof(split_kernels[0]) == spec::NOF_SPECS, "split table writer table");

@@ -6,6 +6,7 @@
  */
 #define LDPC_SPEC_TU_GRAPHS LDPC_SPEC_GRAPHS_SMALL_K
 #include "ldpc_decode_body.h"
+#include "ldpc_hip_launch.h"
 
 namespace ldpc_hip {
 

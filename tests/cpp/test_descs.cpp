@@ -1,0 +1,494 @@
+/* Host test of the descriptor translations (csrc/ldpc_hip_descs.h): every work item field by field for valid
+ * descriptors, one rejection per reason, the order of the checks, and the one-CB / plan equivalence. Links the
+ * host-only units alone (no HIP runtime); built with AddressSanitizer and UBSan by tests/test_descs_host.py.
+ * The expected reasons are the texts of the entry points' errors before the translations were gathered in one unit. */
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ldpc_hip_descs.h"
+
+using namespace ldpc_hip;
+
+static int g_failed = 0;
+#define CHECK(cond)                                                                                                    \
+  do {                                                                                                                 \
+    if (!(cond)) {                                                                                                     \
+      std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);                                                      \
+      ++g_failed;                                                                                                      \
+    }                                                                                                                  \
+  } while (0)
+
+static void expect_reason(const char* got, const char* want, int line)
+{
+  if (got == nullptr || std::strcmp(got, want) != 0) {
+    std::printf("FAIL line %d: reason \"%s\", expected \"%s\"\n", line, got != nullptr ? got : "(accepted)", want);
+    ++g_failed;
+  }
+}
+#define REASON(got, want) expect_reason(got, want, __LINE__)
+
+static const char* const R_DEC_GRAPH  = "invalid base graph / lifting size";
+static const char* const R_DEC_ITER   = "Max iterations must be different to 0";
+static const char* const R_DEC_LEN    = "input length out of range [(K+2)Z, N_short Z]";
+static const char* const R_DEC_FILL   = "invalid number of filler bits";
+static const char* const R_DEC_MODE   = "invalid CRC mode";
+static const char* const R_DEC_POLY   = "invalid CRC polynomial";
+static const char* const R_DEC_SCALE  = "Scaling factor must be between 0 and 1 exclusively";
+static const char* const R_DM_PARAMS  = "invalid rv / modulation / rm_length";
+static const char* const R_DM_LARGE   = "N_ref / cb_length too large";
+static const char* const R_DM_LEN     = "LDPC rate dematching: invalid input length.";
+static const char* const R_DM_FILL    = "LDPC rate dematching: invalid number of filler bits.";
+static const char* const R_DM_PAIRED  = "dematch_decode_launch: dematch descriptor does not match its codeblock "
+                                        "(cb_length != llr_length or filler bits differ)";
+/* the one wording of what were "demod_dematch_launch: symbols x bits per symbol must equal rm_length",
+ * "demod_dematch_launch: rm_length above 32768 (use demodulate + dematch)" and the fused launch's text below */
+static const char* const R_DM_DEMOD   = "demod_dematch_launch: symbols x bits per symbol must equal rm_length <= 32768";
+static const char* const R_DM_DEMOD_F = "dematch_decode_launch: symbols x bits per symbol must equal rm_length <= 32768";
+static const char* const R_DM_SCR     = "scrambled codeblock with rm_length above 32768 cannot be descrambled in the "
+                                        "dematcher: descramble it with ldpc_hip_descramble_launch first";
+
+static ldpc_hip_dec_desc dec_desc(int bg, unsigned Z)
+{
+  ldpc_hip_dec_desc d{};
+  d.base_graph      = static_cast<uint8_t>(bg);
+  d.max_iterations  = 8;
+  d.crc_mode        = LDPC_HIP_CRC_MODE_EARLY_STOP;
+  d.crc_poly        = 1;
+  d.lifting_size    = static_cast<uint16_t>(Z);
+  d.nof_filler_bits = 0;
+  d.llr_length      = (bg == 1 ? 66U : 50U) * Z;
+  d.scaling_factor  = 0.0f;
+  d.llr_offset      = 4096;
+  d.out_offset      = 512;
+  return d;
+}
+
+static ldpc_hip_dematch_desc dm_desc(int bg, unsigned Z, unsigned Qm, unsigned E)
+{
+  ldpc_hip_dematch_desc d{};
+  d.modulation_order = static_cast<uint8_t>(Qm);
+  d.rv               = 2;
+  d.new_data         = 1;
+  d.cb_length        = (bg == 1 ? 66U : 50U) * Z;
+  d.rm_length        = E;
+  d.Nref             = 0;
+  d.nof_filler_bits  = 0;
+  return d;
+}
+
+static const char* dematch(const ldpc_hip_dematch_desc& s, dematch_cb& out, const ldpc_hip_demod_desc* demod = nullptr,
+                           const ldpc_hip_scramble_desc* scr = nullptr, const dec_cb* paired = nullptr)
+{
+  static int8_t llr[4], soft[4];
+  static float  sym[64], nv[64];
+  return make_dematch_cb(s, llr, soft, demod, sym, nv, scr, paired, out);
+}
+
+/* the generator's registers, bit by bit (TS 38.211 5.2.1): 31 bits from bit Nc + offset */
+static ldpc_hip_prs_state prs_reference(uint32_t c_init, uint32_t offset)
+{
+  const uint32_t       n = 1600 + offset + 31;
+  std::vector<uint8_t> x1(n + 31, 0), x2(n + 31, 0);
+  x1[0] = 1;
+  for (int i = 0; i != 31; ++i) {
+    x2[i] = (c_init >> i) & 1U;
+  }
+  for (uint32_t i = 0; i != n; ++i) {
+    x1[i + 31] = x1[i + 3] ^ x1[i];
+    x2[i + 31] = x2[i + 3] ^ x2[i + 2] ^ x2[i + 1] ^ x2[i];
+  }
+  ldpc_hip_prs_state st{0, 0};
+  for (int i = 0; i != 31; ++i) {
+    st.x1 |= static_cast<uint32_t>(x1[1600 + offset + i]) << i;
+    st.x2 |= static_cast<uint32_t>(x2[1600 + offset + i]) << i;
+  }
+  return st;
+}
+
+static void test_decode_valid()
+{
+  const struct {
+    int      bg;
+    unsigned Z;
+  } graphs[] = {{1, 384}, {2, 36}, {2, 2}};
+  for (const auto& g : graphs) {
+    ldpc_hip_dec_desc d = dec_desc(g.bg, g.Z);
+    d.nof_filler_bits   = static_cast<uint16_t>(g.Z - 1);
+    d.crc_mode          = LDPC_HIP_CRC_MODE_EARLY_STOP | LDPC_HIP_CRC_MODE_FLAG_KEEP_PASSED;
+    dec_cb c;
+    std::memset(&c, 0xa5, sizeof(c));
+    CHECK(make_dec_cb(d, c) == nullptr);
+    CHECK(c.llr_offset == 4096 && c.out_offset == 512 && c.llr_length == d.llr_length && c.result_index == 0);
+    CHECK(c.nof_filler_bits == g.Z - 1 && c.max_iterations == 8);
+    CHECK(c.crc_mode == LDPC_HIP_CRC_MODE_EARLY_STOP && c.keep_passed == 1 && c.crc_poly == 1);
+    CHECK(c.pad[0] == 0 && c.pad[1] == 0);
+    CHECK(c.scaling_factor == 0.8f); /* 0 selects the default */
+    /* the shortest and the longest input */
+    d.llr_length = ((g.bg == 1 ? 22U : 10U) + 2U) * g.Z;
+    CHECK(make_dec_cb(d, c) == nullptr && c.llr_length == d.llr_length);
+    /* no CRC: the polynomial is ignored and forced to 0 */
+    d.crc_mode = LDPC_HIP_CRC_MODE_NONE;
+    d.crc_poly = 7;
+    CHECK(make_dec_cb(d, c) == nullptr && c.crc_mode == 0 && c.crc_poly == 0 && c.keep_passed == 0);
+    d.crc_mode       = LDPC_HIP_CRC_MODE_CHECK_AFTER;
+    d.crc_poly       = 2;
+    d.scaling_factor = 0.75f;
+    CHECK(make_dec_cb(d, c) == nullptr && c.crc_mode == 2 && c.crc_poly == 2 && c.scaling_factor == 0.75f);
+    CHECK(graph_slot(g.bg, g.Z) == (g.bg - 1) * 51 + lifting_position(g.Z));
+    CHECK(msg_bytes_of(g.bg, g.Z) == ((g.bg == 1 ? 22U : 10U) * g.Z + 7U) / 8U);
+  }
+}
+
+static void test_decode_rejections()
+{
+  dec_cb                  c;
+  const ldpc_hip_dec_desc ok = dec_desc(1, 384);
+  ldpc_hip_dec_desc       d  = ok;
+  d.base_graph = 3;
+  REASON(make_dec_cb(d, c), R_DEC_GRAPH);
+  d = ok, d.lifting_size = 37;
+  REASON(make_dec_cb(d, c), R_DEC_GRAPH);
+  d = ok, d.max_iterations = 0;
+  REASON(make_dec_cb(d, c), R_DEC_ITER);
+  d = ok, d.llr_length = 24U * 384U - 1U;
+  REASON(make_dec_cb(d, c), R_DEC_LEN);
+  d = ok, d.llr_length = 66U * 384U + 1U;
+  REASON(make_dec_cb(d, c), R_DEC_LEN);
+  d = dec_desc(2, 36), d.llr_length = 12U * 36U - 1U;
+  REASON(make_dec_cb(d, c), R_DEC_LEN);
+  d = dec_desc(2, 36), d.llr_length = 50U * 36U + 1U;
+  REASON(make_dec_cb(d, c), R_DEC_LEN);
+  d = ok, d.nof_filler_bits = 22U * 384U;
+  REASON(make_dec_cb(d, c), R_DEC_FILL);
+  d = ok, d.crc_mode = 3;
+  REASON(make_dec_cb(d, c), R_DEC_MODE);
+  d = ok, d.crc_mode = 3 | LDPC_HIP_CRC_MODE_FLAG_KEEP_PASSED;
+  REASON(make_dec_cb(d, c), R_DEC_MODE);
+  d = ok, d.crc_poly = 3;
+  REASON(make_dec_cb(d, c), R_DEC_POLY);
+  d = ok, d.crc_poly = -1;
+  REASON(make_dec_cb(d, c), R_DEC_POLY);
+  d = ok, d.scaling_factor = 1.0f;
+  REASON(make_dec_cb(d, c), R_DEC_SCALE);
+  d = ok, d.scaling_factor = -0.5f;
+  REASON(make_dec_cb(d, c), R_DEC_SCALE);
+  /* order: graph, iterations, length, filler bits, CRC mode, CRC polynomial, scaling factor */
+  d = ok, d.scaling_factor = 2.0f, d.crc_poly = 5;
+  REASON(make_dec_cb(d, c), R_DEC_POLY);
+  d.crc_mode = 9;
+  REASON(make_dec_cb(d, c), R_DEC_MODE);
+  d.nof_filler_bits = 0xffff;
+  REASON(make_dec_cb(d, c), R_DEC_FILL);
+  d.llr_length = 1;
+  REASON(make_dec_cb(d, c), R_DEC_LEN);
+  d.max_iterations = 0;
+  REASON(make_dec_cb(d, c), R_DEC_ITER);
+  d.lifting_size = 1;
+  REASON(make_dec_cb(d, c), R_DEC_GRAPH);
+}
+
+static void test_plan_order_and_equivalence()
+{
+  /* one CB: the plan's item is the one-CB item */
+  for (const ldpc_hip_dec_desc& d : {dec_desc(1, 384), dec_desc(2, 36), dec_desc(2, 2)}) {
+    dec_cb              one;
+    std::vector<dec_cb> cbs;
+    CHECK(make_dec_cb(d, one) == nullptr && make_dec_cbs(1, &d, cbs) == nullptr && cbs.size() == 1);
+    one.result_index = cbs[0].result_index;
+    CHECK(cbs[0].result_index == 0 && std::memcmp(&one, &cbs[0], sizeof(dec_cb)) == 0);
+  }
+  /* grouped by (BG, Z) in slot order, the default scaling before another, the caller's order inside a group */
+  ldpc_hip_dec_desc d[5] = {dec_desc(2, 36), dec_desc(1, 384), dec_desc(2, 36), dec_desc(1, 384), dec_desc(1, 384)};
+  d[3].scaling_factor    = 0.5f;
+  std::vector<dec_cb> cbs;
+  CHECK(make_dec_cbs(5, d, cbs) == nullptr && cbs.size() == 5);
+  const uint32_t want[5] = {1, 4, 3, 0, 2};
+  for (int i = 0; i != 5; ++i) {
+    CHECK(cbs[i].result_index == want[i]);
+  }
+  CHECK(cbs[2].scaling_factor == 0.5f && cbs[1].scaling_factor == 0.8f);
+  /* the first invalid descriptor in the caller's order decides the reason; nothing is produced */
+  d[4].max_iterations = 0;
+  d[2].crc_mode       = 3;
+  cbs.clear();
+  REASON(make_dec_cbs(5, d, cbs), R_DEC_MODE);
+  CHECK(cbs.empty());
+  CHECK(make_dec_cbs(0, nullptr, cbs) == nullptr && cbs.empty());
+}
+
+static void test_hw_config()
+{
+  ldpc_hip_hw_config cfg{};
+  cfg.base_graph              = 2;
+  cfg.lifting_size            = 36;
+  cfg.nof_filler_bits         = 8;
+  cfg.max_nof_ldpc_iterations = 6;
+  cfg.use_early_stop          = 1;
+  cfg.cb_crc_type             = 2;
+  ldpc_hip_dec_desc x = make_dec_desc_from_hw(cfg, 1800, 1234, 96);
+  CHECK(x.base_graph == 2 && x.lifting_size == 36 && x.nof_filler_bits == 8 && x.max_iterations == 6);
+  CHECK(x.crc_mode == LDPC_HIP_CRC_MODE_EARLY_STOP && x.crc_poly == 2 && x.llr_length == 1800);
+  CHECK(x.scaling_factor == 0.8f && x.llr_offset == 1234 && x.out_offset == 96);
+  cfg.use_early_stop = 0;
+  x                  = make_dec_desc_from_hw(cfg, 1800, 0, 0);
+  CHECK(x.crc_mode == LDPC_HIP_CRC_MODE_CHECK_AFTER);
+  dec_cb c;
+  CHECK(make_dec_cb(x, c) == nullptr);
+}
+
+static void test_dematch_valid()
+{
+  static int8_t llr[4], soft[4];
+  static float  sym[64], nv[64];
+  const struct {
+    int      bg;
+    unsigned Z, Qm, E;
+  } cases[] = {{1, 384, 8, 30000}, {2, 36, 2, 1248}, {2, 2, 1, 77}, {1, 384, 6, 32784 * 3}};
+  for (const auto& k : cases) {
+    ldpc_hip_dematch_desc s = dm_desc(k.bg, k.Z, k.Qm, k.E);
+    s.Nref                  = s.cb_length - 1;
+    s.nof_filler_bits       = k.Z - 1;
+    dematch_cb c;
+    std::memset(static_cast<void*>(&c), 0xa5, sizeof(c));
+    CHECK(make_dematch_cb(s, llr + 1, soft + 2, nullptr, nullptr, nullptr, nullptr, nullptr, c) == nullptr);
+    CHECK(c.llr == llr + 1 && c.soft == soft + 2 && c.sym == nullptr && c.nv == nullptr);
+    CHECK(c.cb_length == s.cb_length && c.rm_length == k.E && c.Nref == s.cb_length - 1);
+    CHECK(c.nof_filler_bits == k.Z - 1 && c.modulation_order == k.Qm && c.rv == 2 && c.new_data == 1);
+    CHECK(c.demod == 0 && c.stage_bytes == 0 && c.scr_x1 == 0 && c.scr_x2 == 0);
+    /* a disabled scrambling descriptor changes nothing, whatever the length */
+    const ldpc_hip_scramble_desc off{12345, 0, {0, 0, 0}, 99};
+    dematch_cb                   c2;
+    CHECK(make_dematch_cb(s, llr + 1, soft + 2, nullptr, nullptr, nullptr, &off, nullptr, c2) == nullptr);
+    CHECK(std::memcmp(&c, &c2, sizeof(c)) == 0);
+  }
+  /* demodulated: 64-QAM, 200 symbols */
+  ldpc_hip_dematch_desc s = dm_desc(2, 36, 6, 1200);
+  ldpc_hip_demod_desc   m{};
+  m.symbol_offset = 5;
+  m.noise_offset  = 7;
+  m.nof_symbols   = 200;
+  m.modulation    = 6;
+  dematch_cb c;
+  CHECK(make_dematch_cb(s, llr, soft, &m, sym, nv, nullptr, nullptr, c) == nullptr);
+  CHECK(c.llr == nullptr && c.soft == soft && c.sym == sym + 10 && c.nv == nv + 7 && c.demod == 6);
+  CHECK(c.rm_length == 1200 && c.modulation_order == 6 && c.scr_x1 == 0);
+  /* BPSK and pi/2-BPSK (modulation 0 and 1) both carry one bit per symbol */
+  s = dm_desc(2, 36, 1, 200), m.modulation = 0;
+  CHECK(make_dematch_cb(s, llr, soft, &m, sym, nv, nullptr, nullptr, c) == nullptr && c.demod == 0 && c.sym == sym + 10);
+  /* scrambled: the start state is ldpc_hip_prs_init's (prs_state_at), checked against the registers bit by bit */
+  for (const uint32_t offset : {0U, 1U, 31U, 12345U}) {
+    const ldpc_hip_scramble_desc scr{0x1234567U, 1, {0, 0, 0}, offset};
+    s = dm_desc(1, 384, 4, 32768);
+    CHECK(make_dematch_cb(s, llr, soft, nullptr, nullptr, nullptr, &scr, nullptr, c) == nullptr);
+    const ldpc_hip_prs_state at = prs_state_at(0x1234567U, offset), ref = prs_reference(0x1234567U, offset);
+    CHECK(at.x1 == ref.x1 && at.x2 == ref.x2 && at.x1 != 0);
+    CHECK(c.scr_x1 == ref.x1 && c.scr_x2 == ref.x2 && c.llr == llr);
+  }
+  /* fused: the decode work item it feeds agrees */
+  dec_cb                  cb;
+  const ldpc_hip_dec_desc dd = dec_desc(2, 36);
+  CHECK(make_dec_cb(dd, cb) == nullptr);
+  s = dm_desc(2, 36, 2, 1248);
+  CHECK(make_dematch_cb(s, llr, soft, nullptr, nullptr, nullptr, nullptr, &cb, c) == nullptr && c.cb_length == 1800);
+}
+
+static void test_dematch_rejections()
+{
+  dematch_cb                  c;
+  const ldpc_hip_dematch_desc ok = dm_desc(2, 36, 2, 1248);
+  ldpc_hip_dematch_desc       s  = ok;
+  s.rv = 4;
+  REASON(dematch(s, c), R_DM_PARAMS);
+  s = ok, s.modulation_order = 3;
+  REASON(dematch(s, c), R_DM_PARAMS);
+  s = ok, s.modulation_order = 4, s.rm_length = 1250;
+  REASON(dematch(s, c), R_DM_PARAMS);
+  s = ok, s.cb_length = 1801;
+  REASON(dematch(s, c), R_DM_LEN);
+  s = ok, s.cb_length = 50 * 37; /* 37 is no lifting size */
+  REASON(dematch(s, c), R_DM_LEN);
+  s = ok, s.cb_length = 66 * 385;
+  REASON(dematch(s, c), R_DM_LARGE);
+  s = ok, s.Nref = 66 * 384 + 1;
+  REASON(dematch(s, c), R_DM_LARGE);
+  s = ok, s.nof_filler_bits = 8 * 36;
+  REASON(dematch(s, c), R_DM_FILL);
+  s = dm_desc(1, 384, 2, 1248), s.nof_filler_bits = 20 * 384;
+  REASON(dematch(s, c), R_DM_FILL);
+  /* demodulated */
+  ldpc_hip_demod_desc m{};
+  m.nof_symbols = 623; /* x 2 = 1246 */
+  m.modulation  = 2;
+  REASON(dematch(ok, c, &m), R_DM_DEMOD);
+  m.nof_symbols = 624, m.modulation = 4; /* bits per symbol differ from Qm */
+  REASON(dematch(ok, c, &m), R_DM_DEMOD);
+  m.modulation = 3;
+  REASON(dematch(ok, c, &m), R_DM_DEMOD);
+  s = dm_desc(1, 384, 2, 32784), m.modulation = 2, m.nof_symbols = 16392;
+  REASON(dematch(s, c, &m), R_DM_DEMOD);
+  dec_cb                  cb;
+  const ldpc_hip_dec_desc dd = dec_desc(1, 384);
+  CHECK(make_dec_cb(dd, cb) == nullptr);
+  REASON(dematch(s, c, &m, nullptr, &cb), R_DM_DEMOD_F);
+  /* scrambled */
+  const ldpc_hip_scramble_desc scr{1, 1, {0, 0, 0}, 0};
+  REASON(dematch(s, c, nullptr, &scr), R_DM_SCR);
+  s.rm_length = 32768;
+  CHECK(dematch(s, c, nullptr, &scr) == nullptr);
+  /* fused: length or filler bits differ from the decode item */
+  cb.llr_length -= 384;
+  REASON(dematch(s, c, nullptr, nullptr, &cb), R_DM_PAIRED);
+  cb.llr_length += 384, cb.nof_filler_bits = 1;
+  REASON(dematch(s, c, nullptr, nullptr, &cb), R_DM_PAIRED);
+  cb.nof_filler_bits = 0;
+  /* order: descriptor, then the fused pair, then the demodulator, then scrambling */
+  s = dm_desc(1, 384, 2, 32784), m.nof_symbols = 1;
+  REASON(dematch(s, c, &m, &scr, &cb), R_DM_DEMOD_F);
+  cb.nof_filler_bits = 1;
+  REASON(dematch(s, c, &m, &scr, &cb), R_DM_PAIRED);
+  s.nof_filler_bits = 20 * 384;
+  REASON(dematch(s, c, &m, &scr, &cb), R_DM_FILL);
+  s.Nref = 1U << 20;
+  REASON(dematch(s, c, &m, &scr, &cb), R_DM_LARGE);
+  s.rv = 7;
+  REASON(dematch(s, c, &m, &scr, &cb), R_DM_PARAMS);
+  m.nof_symbols = 16392;
+  REASON(dematch(dm_desc(1, 384, 2, 32784), c, &m, &scr), R_DM_DEMOD); /* the demodulator before scrambling */
+}
+
+static void test_encoder()
+{
+  enc_cb            e;
+  ldpc_hip_enc_desc d{64, 128, 66 * 384, 384, 1, 0};
+  CHECK(make_enc_cb(d, nullptr, e) == nullptr);
+  CHECK(e.msg_offset == 64 && e.cw_offset == 128 && e.cw_length == 66 * 384 && e.graph_slot == graph_slot(1, 384));
+  CHECK(e.msg_bit_off == 0 && e.data_bits == 22 * 384 && e.crc_at == 0 && e.pad == 0);
+  const uint32_t ext[3] = {5, 8000, 8424};
+  CHECK(make_enc_cb(d, ext, e) == nullptr && e.msg_bit_off == 5 && e.data_bits == 8000 && e.crc_at == 8424);
+  ldpc_hip_enc_desc d2{0, 0, 100, 2, 2, 0};
+  CHECK(make_enc_cb(d2, nullptr, e) == nullptr && e.graph_slot == 51 && e.data_bits == 20);
+  d2.lifting_size = 1;
+  REASON(make_enc_cb(d2, nullptr, e), "encode_launch: invalid base graph / lifting size");
+  d2 = d, d2.base_graph = 0;
+  REASON(make_enc_cb(d2, nullptr, e), "encode_launch: invalid base graph / lifting size");
+  d2 = d, d2.cw_length = 0;
+  REASON(make_enc_cb(d2, nullptr, e), "encode_launch: codeword length out of range");
+  d2.cw_length = 66 * 384 + 1;
+  REASON(make_enc_cb(d2, nullptr, e), "encode_launch: codeword length out of range");
+  const uint32_t bad_off[3] = {8, 8000, 0}, bad_data[3] = {0, 8449, 0}, bad_crc[3] = {0, 8000, 8425},
+                 bad_crc2[3] = {0, 8300, 8200};
+  REASON(make_enc_cb(d, bad_off, e), "encode_launch: message bit range out of range");
+  REASON(make_enc_cb(d, bad_data, e), "encode_launch: message bit range out of range");
+  REASON(make_enc_cb(d, bad_crc, e), "encode_launch: message bit range out of range");
+  REASON(make_enc_cb(d, bad_crc2, e), "encode_launch: message bit range out of range");
+  REASON(make_enc_cb(d2, bad_off, e), "encode_launch: codeword length out of range"); /* order */
+}
+
+static void test_rate_matcher()
+{
+  ratematch_cb     r;
+  ldpc_hip_rm_desc d{32, 96, 66 * 384, 30000, 0, 100, 8, 2};
+  CHECK(make_rm_cb(d, r) == nullptr);
+  CHECK(r.cw_offset == 32 && r.out_offset == 96 && r.cb_length == 25344 && r.rm_length == 30000 && r.Ncb == 25344);
+  CHECK(r.k0 == 33 * 384 && r.fill_lo == 20 * 384 - 100 && r.fill_hi == 20 * 384 && r.Qm == 8 && r.pad == 0);
+  d.Nref = 20000; /* limited buffer: k0 = floor(33 Ncb / N) Z */
+  CHECK(make_rm_cb(d, r) == nullptr && r.Ncb == 20000 && r.k0 == (33U * 20000U / 25344U) * 384U);
+  ldpc_hip_rm_desc d2{0, 0, 50 * 36, 1248, 0, 0, 2, 3};
+  CHECK(make_rm_cb(d2, r) == nullptr && r.k0 == 43 * 36 && r.fill_lo == 8 * 36 && r.fill_hi == 8 * 36);
+  d2.cb_length = 100; /* BG2 Z = 2 */
+  CHECK(make_rm_cb(d2, r) == nullptr && r.k0 == 43 * 2);
+  d2.cb_length = 1801;
+  REASON(make_rm_cb(d2, r), "rate_match_launch: invalid codeblock length");
+  d2.cb_length = 50 * 37;
+  REASON(make_rm_cb(d2, r), "rate_match_launch: invalid parameters");
+  d2.cb_length = 1800, d2.rv = 4;
+  REASON(make_rm_cb(d2, r), "rate_match_launch: invalid parameters");
+  d2.rv = 0, d2.modulation_order = 0;
+  REASON(make_rm_cb(d2, r), "rate_match_launch: invalid parameters");
+  d2.modulation_order = 9;
+  REASON(make_rm_cb(d2, r), "rate_match_launch: invalid parameters");
+  d2.modulation_order = 2, d2.rm_length = 0;
+  REASON(make_rm_cb(d2, r), "rate_match_launch: invalid parameters");
+  d2.rm_length = 1249;
+  REASON(make_rm_cb(d2, r), "rate_match_launch: invalid parameters");
+  d2.rm_length = 1248, d2.nof_filler_bits = 8 * 36;
+  REASON(make_rm_cb(d2, r), "rate_match_launch: invalid number of filler bits");
+  d2.rv = 4;
+  REASON(make_rm_cb(d2, r), "rate_match_launch: invalid parameters"); /* order */
+}
+
+static void test_pdsch()
+{
+  pdsch_enc_cb      c;
+  ldpc_hip_enc_desc ed{64, 0, 50 * 36, 36, 2, 0};
+  ldpc_hip_rm_desc  rd{0, 96, 50 * 36, 1248, 0, 0, 2, 0};
+  const uint32_t    ext[3] = {0, 300, 0};
+  CHECK(make_pdsch_cb(ed, ext, rd, c) == nullptr);
+  CHECK(c.enc.graph_slot == graph_slot(2, 36) && c.enc.data_bits == 300 && c.rm.rm_length == 1248 && c.rm.out_offset == 96);
+  ed.cw_length = 40 * 36;
+  REASON(make_pdsch_cb(ed, ext, rd, c), "pdsch_encode: encoder and rate matcher descriptors disagree");
+  ed.cw_length = 0;
+  REASON(make_pdsch_cb(ed, ext, rd, c), "encode_launch: codeword length out of range");
+  ed.cw_length = 50 * 36, rd.rv = 4;
+  REASON(make_pdsch_cb(ed, ext, rd, c), "rate_match_launch: invalid parameters");
+  /* the lengths agree, the base graphs do not: 1800 bits are a whole BG2 codeword and a BG1 codeword's start */
+  rd.rv = 0, ed.base_graph = 1;
+  REASON(make_pdsch_cb(ed, ext, rd, c), "pdsch_encode: encoder and rate matcher descriptors disagree");
+}
+
+static void test_tb_join()
+{
+  /* msg_offset, tb_offset, msg_stride, tbs, result_index, nof_cbs, cb_msg_bits, nof_filler_bits, cb_crc_bits, pad */
+  const ldpc_hip_tb_desc one{0, 0, 45, 256, 0, 1, 360, 80, 24, 0};
+  CHECK(tb_desc_reason(one) == nullptr);
+  const ldpc_hip_tb_desc two{0, 0, 1056, 16000, 0, 2, 8448, 412, 24, 0}; /* kd = 8012: 16000 - 8012 + 24 = 8012 */
+  CHECK(tb_desc_reason(two) == nullptr);
+  ldpc_hip_tb_desc d = one;
+  d.nof_cbs = 0;
+  REASON(tb_desc_reason(d), "tb_join: invalid sizes");
+  d = one, d.tbs = 0;
+  REASON(tb_desc_reason(d), "tb_join: invalid sizes");
+  d = one, d.tbs = 250;
+  REASON(tb_desc_reason(d), "tb_join: invalid sizes");
+  d = one, d.msg_stride = 44;
+  REASON(tb_desc_reason(d), "tb_join: invalid sizes");
+  d = one, d.cb_crc_bits = 8;
+  REASON(tb_desc_reason(d), "tb_join: CRC length must be 16 or 24");
+  d = two, d.tbs = 8U * 4096U * 64U + 8U;
+  REASON(tb_desc_reason(d), "tb_join: transport block too large");
+  d = one, d.tbs = 264;
+  REASON(tb_desc_reason(d), "tb_join: TB larger than its codeblock");
+  d = two, d.cb_crc_bits = 16;
+  REASON(tb_desc_reason(d), "tb_join: segmentation inconsistent with the TB size");
+  d = two, d.tbs = 8008; /* fits one codeblock */
+  REASON(tb_desc_reason(d), "tb_join: segmentation inconsistent with the TB size");
+  d = two, d.tbs = 16008;
+  REASON(tb_desc_reason(d), "tb_join: segmentation inconsistent with the TB size");
+  d = two, d.nof_filler_bits = 8448 - 24;
+  REASON(tb_desc_reason(d), "tb_join: segmentation inconsistent with the TB size");
+  d = two, d.cb_crc_bits = 8, d.tbs = 4; /* order: sizes before the CRC length */
+  REASON(tb_desc_reason(d), "tb_join: invalid sizes");
+}
+
+int main()
+{
+  CHECK(align16(0) == 0 && align16(1) == 16 && align16(16) == 16 && align16(17) == 32);
+  CHECK(align16((1ULL << 32) + 1) == (1ULL << 32) + 16);
+  CHECK(valid_modulation(0) && valid_modulation(8) && !valid_modulation(3) && !valid_modulation(10));
+  CHECK(bits_per_symbol(0) == 1 && bits_per_symbol(1) == 1 && bits_per_symbol(6) == 6);
+  CHECK(graph_slot(1, 2) == 0 && graph_slot(2, 384) == 101 && graph_slot(0, 2) == -1 && graph_slot(1, 1) == -1);
+  test_decode_valid();
+  test_decode_rejections();
+  test_plan_order_and_equivalence();
+  test_hw_config();
+  test_dematch_valid();
+  test_dematch_rejections();
+  test_encoder();
+  test_rate_matcher();
+  test_pdsch();
+  test_tb_join();
+  std::printf(g_failed == 0 ? "test_descs: all passed\n" : "test_descs: %d checks failed\n", g_failed);
+  return g_failed == 0 ? 0 : 1;
+}

@@ -2,7 +2,7 @@
 
 Round 4 passed hipStreamLegacy ((hipStream_t)1) through to the runtime and a multi-group plan's fork crashed in it;
 the ABI now maps hipStreamLegacy to the null stream and passes hipStreamPerThread ((hipStream_t)2) to the runtime,
-which resolves it (ldpc_hip_api.cpp abi_stream; the probe of every runtime call the fork makes is
+which resolves it (ldpc_hip_ctx.h abi_stream; the probe of every runtime call the fork makes is
 tools/ubench/stream_probe.hip). Every *_launch entry point and the multi-group fork run here on both handles,
 bit-exact vs the oracle. The Python wrappers now join torch's current stream for a stream of 0 / None
 (srsran_projectvtlmo_amd._lib.stream_arg) instead of synchronising it on the host; the last test pins the ordering
