@@ -1,9 +1,10 @@
 """CPU ORACLE for the MI355X LDPC decode path -- TEST INFRASTRUCTURE ONLY.
 
 ctypes/numpy wrapper around `oracle/ldpc_oracle.c`, the plain-C restatement of the reference algorithms (see
-`oracle/ldpc_oracle.h` for per-function citations and the parity-pinning status: PARTIALLY PINNED by the
-reference's in-source known-answer tests and round-trip properties; the reference's .dat fixtures are absent and
-building/running the reference is denied).
+`oracle/ldpc_oracle.h` for per-function citations). Pinned by the reference's in-source known-answer tests and
+round-trip properties, and directly by the compiled reference: `oracle/ref.py` wraps `oracle/_ref/libsrsran_ref.so`
+(`make -C oracle ref`) with the same call shapes, tests/test_oracle_vs_reference.py compares the two, and
+tests/golden/ref_*.npz record the reference's outputs.
 
 Only `tests/`, `__graft_entry__.smoke()` and `bench.py`'s cpu_baseline leg may import this package, and only as the
 checker. The product package `srsran_projectvtlmo_amd` never imports it.

@@ -976,7 +976,8 @@ int orc_demodulate_soft(int mod, unsigned nof_symbols, const float* sym, const f
         o[0] = orc_qpsk(re, n);
         o[1] = orc_qpsk(im, n);
         break;
-      case 4: /* demodulation_mapper_qam16.cpp:230-273 (scalar loop), demod_16QAM_symbol_01/_23 :201-228 */
+      case 4: /* demodulation_mapper_qam16.cpp:230-273 (scalar loop), demod_16QAM_symbol_01/_23 :196-223,
+               * range limit 20 (:36) like the 64- and 256-QAM mappers; only BPSK and QPSK use 24 */
         if (orc_near_zero(re, im)) {
           memset(o, 0, 4);
           break;
@@ -993,10 +994,10 @@ int orc_demodulate_soft(int mod, unsigned nof_symbols, const float* sym, const f
             l01 = 2 * l01 - copysignf(0.8F, x);
           }
           l01 /= n;
-          o[c]      = orc_llr_quantize(l01, 24.0F);
+          o[c]      = orc_llr_quantize(l01, 20.0F);
           float l23 = 0.8F - 4 * s10 * fabsf(x);
           l23 /= n;
-          o[2 + c] = orc_llr_quantize(l23, 24.0F);
+          o[2 + c] = orc_llr_quantize(l23, 20.0F);
         }
         break;
       case 6: /* demodulation_mapper_qam64.cpp:404-463 (scalar loop, range limit 20) */

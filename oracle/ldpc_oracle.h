@@ -5,12 +5,12 @@
  * check the HIP product path; only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it.
  * The product library (srsran_projectvtlmo_amd/) never links or calls anything in this directory.
  *
- * Parity status: PARTIALLY PINNED. The reference's golden .dat fixtures are absent from the snapshot and building
- * or running the reference is denied, so this restatement is pinned by (i) the reference's in-source
- * known-answer tests (log_likelihood_ratio_test.cpp:32-87, crc_calculator_test.cpp:32-110,
- * ldpc_enc_dec_test.cpp:334-358, hard_decision_test.cpp), (ii) noiseless encode->decode and
- * rate-match->dematch round trips, and (iii) the survey's record that a restatement of the same pseudo-code matched
- * the reference generic decoder bit-exactly on 48/48 randomised cases. See DESIGN.md "Oracle".
+ * Parity status: the decoder, LLR arithmetic, CRC, rate dematcher, rate matcher, encoder and demodulator are pinned
+ * by the compiled reference (oracle/_ref/libsrsran_ref.so through ref_shim.cpp; tests/test_oracle_vs_reference.py
+ * live, tests/golden/ref_*.npz recorded), next to (i) the reference's in-source known-answer tests
+ * (log_likelihood_ratio_test.cpp:32-87, crc_calculator_test.cpp:32-110, ldpc_enc_dec_test.cpp:334-358,
+ * hard_decision_test.cpp) and (ii) noiseless encode->decode and rate-match->dematch round trips. The TB join, the
+ * segmenter beyond its known answers and the slot flow remain restatements. See DESIGN.md section 2.
  *
  * Each function cites the reference file:line it follows.
  */

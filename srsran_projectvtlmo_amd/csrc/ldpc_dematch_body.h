@@ -87,10 +87,10 @@ __device__ __forceinline__ void dm_symbol(float2 z, float nv, uint32_t i, const 
           l01 = 2 * l01 - copysignf(0.8F, x);
         }
         l01 /= nv;
-        o[c]      = dm_quantize(l01, 24.0F);
+        o[c]      = dm_quantize(l01, 20.0F); /* demodulation_mapper_qam16.cpp:36: range limit 20, not QPSK's 24 */
         float l23 = 0.8F - 4 * tab.s10 * fabsf(x);
         l23 /= nv;
-        o[2 + c] = dm_quantize(l23, 24.0F);
+        o[2 + c] = dm_quantize(l23, 20.0F);
       }
     } else {
       const float rn = (nv > 0) ? 1 / nv : 0.0F;

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Generates the committed golden fixtures (tests/golden/*.npz) with the CPU oracle (oracle/ldpc_oracle.c).
 
-These are regression fixtures of the oracle, not reference outputs: the reference's own .dat vectors are absent
-from the snapshot and building or running the reference is denied. The oracle itself is pinned by
-tests/test_oracle.py (the reference's in-source known-answer tests + round-trip properties).
+These c*.npz are regression fixtures of the oracle at the benchmark configurations, not reference outputs (the
+reference's own .dat vectors are absent from the snapshot). The reference's outputs are the ref_*.npz next to them,
+recorded by make_reference_fixtures.py from the compiled reference; the oracle is held to those by tests/test_golden.py,
+to the live reference by tests/test_oracle_vs_reference.py, and to the reference's in-source known answers by
+tests/test_oracle.py.
 
 Contents:
   c1.npz  BG2 Z=52, 1 CB, 6 iterations: message 504 random bits (seed 0) + CRC16 -> 520-bit message -> encoded

@@ -1,10 +1,12 @@
 """CPU tests of the soft-demodulation restatement (oracle/ldpc_oracle.c orc_demodulate_soft).
 
-The reference's demodulation_mapper_test.cpp compares against MATLAB .dat vectors that are absent from the snapshot,
-so these LLRs are pinned by (i) the reference test's own special-case rules (noise variance 0 / inf / negative / NaN
--> LLR 0, symbol 0 -> LLR 0, infinite symbols stay in range: demodulation_mapper_test.cpp:128-346), (ii) the
-TS 38.211 §5.1 constellation: noiseless symbols give the transmitted bits as hard decisions, and (iii) an independent
-numpy float32 restatement of the same per-symbol functions (bit-exact)."""
+The reference's demodulation_mapper_test.cpp compares against MATLAB .dat vectors that are absent from the snapshot.
+These tests need only the oracle: (i) the reference test's own special-case rules (noise variance 0 / inf / negative /
+NaN -> LLR 0, symbol 0 -> LLR 0, infinite symbols stay in range: demodulation_mapper_test.cpp:128-346), (ii) the
+TS 38.211 §5.1 constellation: noiseless symbols give the transmitted bits as hard decisions, and (iii) a numpy float32
+restatement of the same per-symbol functions (bit-exact). (iii) is a second reading by the same authors and once shared
+the oracle's wrong 16-QAM range; the LLR values themselves are pinned by the compiled reference
+(tests/test_oracle_vs_reference.py, tests/golden/ref_demod.npz)."""
 import numpy as np
 import pytest
 
@@ -60,8 +62,10 @@ def _np_demod(mod, sym, nv):
                 l01 = np.where(np.abs(x) > f32(2) * s10, f32(2) * l01 - np.copysign(f32(0.8), x), l01)
                 l01 = (l01 / nv).astype(np.float32)
                 l23 = ((f32(0.8) - (f32(4) * s10) * np.abs(x)) / nv).astype(np.float32)
-                out[:, c] = np.where(nv > 0, _np_quantize(l01, 24), 0)
-                out[:, 2 + c] = np.where(nv > 0, _np_quantize(l23, 24), 0)
+                # demodulation_mapper_qam16.cpp:36: 16-QAM quantises over +-20 like 64- and 256-QAM (only BPSK and
+                # QPSK use +-24); this restatement once shared the oracle's +-24, which the compiled reference refuted
+                out[:, c] = np.where(nv > 0, _np_quantize(l01, 20), 0)
+                out[:, 2 + c] = np.where(nv > 0, _np_quantize(l23, 20), 0)
         else:
             rn = np.where(nv > 0, f32(1) / nv, f32(0)).astype(np.float32)
             if mod == 6:

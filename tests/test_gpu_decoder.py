@@ -150,6 +150,16 @@ def test_scaling_factor_variants():
         llr = random_llrs(rng, 50 * 52, "uniform")
         out_hip, _, out_orc, _ = _decode_both(cc, dec, 2, 52, llr, 5, sf=sf)
         np.testing.assert_array_equal(out_hip, out_orc)
+    # added: BG1's degree-19 rows, one-wave and multi-wave graphs, +-127 and zeros, fillers and a CRC, 0.05 (every
+    # check-to-variable message 0) and 0.99; all graphs at recorded reference outputs: test_gpu_reference_fixtures.py
+    for bg, Z, sf, crc, F in [(1, 384, 0.5, None, 0), (1, 36, 0.9, O.CRC24B, 26), (2, 208, 0.3333, O.CRC16, 0),
+                              (1, 7, 0.75, None, 0), (1, 104, 0.05, None, 0), (2, 384, 0.99, O.CRC24A, 200)]:
+        llr = random_llrs(rng, O.BG_N_SHORT[bg] * Z - 3, "mixed")
+        if F:
+            llr[(O.BG_K[bg] - 2) * Z - F:(O.BG_K[bg] - 2) * Z] = 127
+        out_hip, r_hip, out_orc, r_orc = _decode_both(cc, dec, bg, Z, llr, 3, crc=crc, F=F, sf=sf)
+        assert r_hip == r_orc, f"BG{bg} Z={Z} sf={sf}"
+        np.testing.assert_array_equal(out_hip, out_orc, err_msg=f"BG{bg} Z={Z} sf={sf}")
 
 
 def test_batch_plan_mixed_configs(hip_ctx):

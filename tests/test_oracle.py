@@ -1,6 +1,7 @@
 """CPU tests pinning the oracle (oracle/ldpc_oracle.c) to the reference's own known-answer tests and to
-independent properties. The reference's golden .dat fixtures are absent and the reference may not be built or run
-(SURVEY.md §8c), so these are the pins; see DESIGN.md "Oracle"."""
+independent properties. They need nothing but the oracle, so they run on every checkout. The direct pin is next to
+them: tests/test_oracle_vs_reference.py runs the oracle against the compiled reference (oracle/_ref), and
+tests/test_golden.py holds it to the reference's recorded outputs (tests/golden/ref_*.npz); see DESIGN.md section 2."""
 import numpy as np
 import pytest
 

@@ -6,6 +6,67 @@ import numpy as np
 import oracle as O
 
 
+# ---- seeded generator that is plain integer arithmetic on numpy.uint64 (splitmix64 over a counter) ---------------------
+# The reference fixtures (tests/golden/ref_*.npz) store a seed and a digest instead of their bulk inputs, so the inputs
+# must come out the same on every NumPy: no Generator stream is involved, only wrapping 64-bit multiply, add, shift, xor.
+_SM_GAMMA = np.uint64(0x9E3779B97F4A7C15)
+_SM_M1 = np.uint64(0xBF58476D1CE4E5B9)
+_SM_M2 = np.uint64(0x94D049BB133111EB)
+
+
+def splitmix64(seed: int, n: int) -> np.ndarray:
+    """n 64-bit words: word i is splitmix64's output for the state seed + (i + 1) * gamma."""
+    z = np.full(n, seed & 0xFFFFFFFFFFFFFFFF, np.uint64) + np.arange(1, n + 1, dtype=np.uint64) * _SM_GAMMA
+    z = (z ^ (z >> np.uint64(30))) * _SM_M1
+    z = (z ^ (z >> np.uint64(27))) * _SM_M2
+    return z ^ (z >> np.uint64(31))
+
+
+def sm_ints(seed: int, n: int, lo: int, hi: int) -> np.ndarray:
+    """n integers in [lo, hi) as int64 (the words' top 32 bits, reduced modulo hi - lo)."""
+    return ((splitmix64(seed, n) >> np.uint64(32)) % np.uint64(hi - lo)).astype(np.int64) + lo
+
+
+def sm_unit(seed: int, n: int) -> np.ndarray:
+    """n float64 in [0, 1): the words' top 53 bits times 2^-53, exact."""
+    return (splitmix64(seed, n) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+
+def sm_bits(seed: int, n: int) -> np.ndarray:
+    return (splitmix64(seed, n) >> np.uint64(63)).astype(np.uint8)
+
+
+def sm_llrs(seed: int, n: int, kind: str = "mixed") -> np.ndarray:
+    """int8 LLRs the reference accepts ([-120, 120] and +-127). kinds: 'uniform'; 'mixed' (5 % zeros, 2 % +127,
+    2 % -127); 'harq' (a quarter each of +-127 and +-120 next to uniform values, so that a combine of two such
+    arrays meets inf + inf, inf - inf, a == -b and saturation)."""
+    v = sm_ints(seed, n, -120, 121).astype(np.int8)
+    if kind == "uniform":
+        return v
+    sel = sm_ints(seed ^ 0x5EED5EED, n, 0, 100)
+    if kind == "mixed":
+        v[sel < 5] = 0
+        v[(sel >= 5) & (sel < 7)] = 127
+        v[(sel >= 7) & (sel < 9)] = -127
+    elif kind == "harq":
+        for k, x in enumerate((127, -127, 120, -120, 0, 1, -1, 60, -60)):
+            v[(sel >= 6 * k) & (sel < 6 * k + 6)] = x
+    else:
+        raise ValueError(kind)
+    return v
+
+
+def sm_symbols(seed: int, n: int, mod: int, noise_var: float = 0.05):
+    """Random constellation points plus bounded noise and per-symbol noise variances (symbols complex64, variances
+    float32), from sm_unit by IEEE-exact operations only (no libm call whose last bit may differ between hosts)."""
+    qm = 1 if mod in (0, 1) else mod
+    z = modulate(sm_bits(seed, n * qm), mod).astype(np.complex128)
+    u = sm_unit(seed + 1, 3 * n)
+    w = ((u[:n] - 0.5) + 1j * (u[n:2 * n] - 0.5)) * (np.sqrt(noise_var) * 2.0)
+    nv = (noise_var * (0.5 + 1.5 * u[2 * n:])).astype(np.float32)
+    return (z + w).astype(np.complex64), nv
+
+
 def random_llrs(rng, n, kind="mixed"):
     """int8 LLRs in [-127, 127]. kinds: 'pm10' (reference benchmark: (rgen() & 1)*20 - 10), 'uniform',
     'mixed' (uniform with extra zeros and +-127 infinities)."""
