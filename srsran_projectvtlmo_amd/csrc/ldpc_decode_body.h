@@ -1,432 +1,19 @@
 /*
- * Device code of the LDPC decoder shared by the translation units that instantiate it: ldpc_hip_kernels.hip (generic
- * kernel, the core specialised kernels and the mixed kernel) and ldpc_spec_kernels_*.hip (further specialised
- * kernels, compiled in parallel). Included once per translation unit.
+ * The specialised decoders' bodies: sp::dec (a whole iteration unrolled at compile time from a spec::sgraph) and
+ * sp::qdec (the lane-split decoder of the one-wave graphs, spec::qgraph). decode_cb (ldpc_decode_cb.h) runs them; the
+ * shared helpers, the generic row update, the work-queue loop and the diagnostics, which this header used to hold as
+ * well, are in ldpc_device_util.h, ldpc_decode_row.h, ldpc_dwq_loop.h and ldpc_diag.h.
  */
 #pragma once
-/*
- * gfx950 (MI355X, CDNA4) decoder kernels of the 5G-NR PUSCH LDPC decode path.
- *
- *  ldpc_decode_kernel          layered normalised min-sum decoder, one workgroup per codeblock with the whole decoder
- *                              state resident in LDS: int8 soft bits (N_full x Z) and one compressed check-to-variable
- *                              record per lifted check node (BG1 Z=384: 26 KiB + 75 KiB). Bit-exact with
- *                              ldpc_decoder_generic (lib/phy/upper/channel_coding/ldpc/ldpc_decoder_impl.cpp:60-308,
- *                              ldpc_decoder_generic.cpp:30-128) including the CRC early stop.
- *  ldpc_rate_dematch_kernel    bit de-interleave + rate dematching + HARQ combining
- *                              (ldpc_rate_dematcher_impl.cpp:46-213), one workgroup per codeblock.
- *
- * Work mapping of the decoder. A base-graph row m lifts to Z independent check nodes t. A 64-lane wave takes 64 (or,
- * with edge splitting, 32) consecutive check nodes of one row, so the row -- degree, edge list, shifts -- is
- * wave-uniform and read through the scalar unit, while the Zc cyclic shift is a per-lane LDS byte gather
- * soft[col][(t + shift) mod Z]. The two-minimum search of a check node runs over the row's edges in the reference's
- * order with its strict '<' (first edge wins). Consecutive rows that share no variable node form one step and are
- * updated concurrently, one barrier per step: they read and write disjoint soft bits, so the result is identical to
- * the layer-serial order of ldpc_decoder_impl.cpp:116-123.
- */
-#include <hip/hip_runtime.h>
 
-#include <cstdint>
 #include <utility>
 
-#include "ldpc_hip_device.h"
+#include "ldpc_device_util.h"
+#include "ldpc_diag.h"
 #include "ldpc_spec.h"
 
 namespace ldpc_hip {
-
 namespace {
-
-constexpr int LLR_MAX = 120;
-constexpr int LLR_INF = 127;
-constexpr int LLR_INTERNAL_INF = LLR_MAX + 1; /* decoder-internal infinity, see "Check-to-variable storage" */
-
-__device__ __forceinline__ bool llr_isinf(int v) { return v > LLR_MAX || v < -LLR_MAX; }
-
-/* Wave-wide XOR reduction (wave64): DPP within each 16-lane row (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror,
- * row_mirror), then the four rows' lanes 0, 16, 32, 48 read out as scalars: no LDS round trips (a ds_bpermute
- * butterfly costs six). Every lane gets the total. */
-__device__ __forceinline__ uint32_t wave_xor(uint32_t v)
-{
-  v ^= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0xb1, 0xf, 0xf, false));
-  v ^= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x4e, 0xf, 0xf, false));
-  v ^= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x141, 0xf, 0xf, false));
-  v ^= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x140, 0xf, 0xf, false));
-  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), 0) ^
-                               __builtin_amdgcn_readlane(static_cast<int>(v), 16) ^
-                               __builtin_amdgcn_readlane(static_cast<int>(v), 32) ^
-                               __builtin_amdgcn_readlane(static_cast<int>(v), 48));
-}
-
-/* Wave-wide maximum of non-negative ints, the same DPP pattern as wave_xor; every lane gets the result. */
-__device__ __forceinline__ int wave_max(int v)
-{
-  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0xb1, 0xf, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x4e, 0xf, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false));
-  return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-             max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-
-/* (a(x) * b(x)) mod G(x) over GF(2); a, b of degree < order; poly includes the x^order term. */
-__device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b, int order, uint32_t poly)
-{
-  /* a * b mod poly over GF(2) for a, b < x^order (order <= 24; poly includes its x^order term), Horner over the bits
-   * of b from the top: 32-bit operations only, the remainder reduced at every step */
-  const uint32_t top = 1U << order;
-  uint32_t       r   = 0;
-  for (int i = order - 1; i >= 0; --i) {
-    r <<= 1;
-    r ^= (r & top) ? poly : 0U;
-    r ^= ((b >> i) & 1U) ? a : 0U;
-  }
-  return r;
-}
-
-__device__ __forceinline__ void crc_params(int poly_id, int& order, uint32_t& poly)
-{
-  /* hw_dec_cb_crc_type numbering; polynomials of crc_calculator_generic_impl.cpp:28-56 */
-  if (poly_id == LDPC_HIP_CRC16) {
-    order = 16;
-    poly  = 0x11021U;
-  } else if (poly_id == LDPC_HIP_CRC24B) {
-    order = 24;
-    poly  = 0x1800063U;
-  } else {
-    order = 24;
-    poly  = 0x1864cfbU;
-  }
-}
-
-/* CRC remainder of the first L bits of the packed (MSB-first) message in LDS. Linear decomposition:
- * front-pad to nw 32-bit words (leading zeros do not change a zero-init CRC), remainder =
- * XOR_w [(W_w * x^r mod G) * (x^(32 (nw-1-w)) mod G) mod G]. Block-uniform result. s_table: the poly's LDS copy
- * (CRC_LDS_WORDS: slicing-by-4 tables T_0..T_3, then the powers), so a word's CRC is four independent LDS lookups
- * and its power one more, with no global load on the early-stop path. */
-__device__ uint32_t block_crc(const uint8_t* hb, int L, int poly_id, const uint32_t* s_table, uint32_t* s_red,
-                              const uint32_t* __restrict__ g_mcol)
-{
-  const uint32_t* g_pow = s_table + 4 * 256;
-  int      order;
-  uint32_t poly;
-  crc_params(poly_id, order, poly);
-  const uint32_t mask = (order == 32) ? 0xffffffffU : ((1U << order) - 1U);
-  const int      nw   = (L + 31) / 32;
-  const int      p    = nw * 32 - L;
-  uint32_t       acc  = 0;
-  for (int w = threadIdx.x; w < nw; w += blockDim.x) {
-    /* the multiplier's columns first (global, L2-resident; independent of the message, so their latency overlaps the
-     * LDS reads below) */
-    const uint4* mc = reinterpret_cast<const uint4*>(g_mcol + (nw - 1 - w) * 24);
-    uint4        col[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      col[q] = mc[q];
-    }
-    /* hb is 4-byte aligned (lay.hard): one LDS dword per word, byte-swapped to MSB-first */
-    auto be = [&](int i) -> uint32_t {
-      if (i < 0) {
-        return 0U;
-      }
-      return __builtin_bswap32(*reinterpret_cast<const uint32_t*>(hb + 4 * i));
-    };
-    const uint32_t W   = (p == 0) ? be(w) : ((be(w - 1) << (32 - p)) | (be(w) >> p));
-    const uint32_t crc = (s_table[3 * 256 + (W >> 24)] ^ s_table[2 * 256 + ((W >> 16) & 0xffU)] ^
-                          s_table[256 + ((W >> 8) & 0xffU)] ^ s_table[W & 0xffU]) & mask;
-    /* crc * x^(32 (nw - 1 - w)) mod G: the XOR of the columns of crc's set bits (bits >= order are zero) */
-    const uint32_t cw[24] = {col[0].x, col[0].y, col[0].z, col[0].w, col[1].x, col[1].y, col[1].z, col[1].w,
-                             col[2].x, col[2].y, col[2].z, col[2].w, col[3].x, col[3].y, col[3].z, col[3].w,
-                             col[4].x, col[4].y, col[4].z, col[4].w, col[5].x, col[5].y, col[5].z, col[5].w};
-    uint32_t       prod[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < 24; ++i) {
-      prod[i & 3] ^= cw[i] & (0U - ((crc >> i) & 1U));
-    }
-    acc ^= (prod[0] ^ prod[1]) ^ (prod[2] ^ prod[3]);
-    (void)g_pow;
-  }
-  acc              = wave_xor(acc);
-  const int wave   = threadIdx.x >> 6;
-  const int nwaves = (blockDim.x + 63) >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    s_red[wave] = acc;
-  }
-  __syncthreads();
-  /* lane i reads wave i's word (one LDS read, not a chain of nwaves dependent ones), then a wave XOR */
-  const int lane = threadIdx.x & 63;
-  return wave_xor(lane < nwaves ? s_red[lane] : 0U);
-}
-
-/* hard_decision (log_likelihood_ratio.cpp:226-252) of soft[0, K*Z) into LDS packed bytes.
- * Returns true (block-uniform) iff no soft bit is zero. Eight soft bits per thread come in with one 8-byte LDS read
- * (the soft region extends past K*Z, so the last read stays inside it). The block-wide "any zero" goes through the
- * LDS word *s_flag, which holds the token of the last call that found a zero: token must differ between calls, so
- * the flag never needs a reset (and the kernel's LDS stays all dynamic). ZC: Z when it is a compile-time constant
- * (specialised kernel), else 0. */
-/* Per byte of four soft bits: t = (w & 0x7f..) + 0x7f.. has a byte's bit 7 set iff its low seven bits are not all
- * zero, so (w | ~t) & 0x80.. marks s <= 0 (the hard bit) and ~(w | t) & 0x80.. marks s == 0. gather4 packs the four
- * marks (bits 7, 15, 23, 31) into a nibble, soft bit 0 first: (m >> 7) * 0x80402010 puts mark j at bit 31 - j and
- * every cross term at a bit of its own below 28 or above 31 (no carries). */
-__device__ __forceinline__ uint32_t gather4(uint32_t m) { return ((m >> 7) * 0x80402010U) >> 28; }
-
-template <int ZC = 0>
-__device__ __forceinline__ bool block_hard_decision(const int8_t* soft, uint8_t* hb, int KZ, uint32_t* s_flag,
-                                                    uint32_t token, int Z = 0, int stride = 0, int read_off = 0)
-{
-  const int nb   = (KZ + 7) / 8;
-  bool      zero = false;
-  const int zc = ZC > 0 ? ZC : Z;
-  for (int b = threadIdx.x; b < nb; b += blockDim.x) {
-    int pos = 8 * b;
-    if (stride != 0) {
-      /* column-strided copies (specialised kernel, Z % 8 == 0: the 8 bits of a byte share a column) */
-      const int col = pos / zc;
-      pos           = col * stride + read_off + (pos - col * zc);
-    }
-    const uint2    w     = *reinterpret_cast<const uint2*>(soft + pos);
-    const uint32_t keep  = 0xff00U >> min(8, KZ - 8 * b); /* valid bits of the last byte */
-    const uint32_t tx    = (w.x & 0x7f7f7f7fU) + 0x7f7f7f7fU, ty = (w.y & 0x7f7f7f7fU) + 0x7f7f7f7fU;
-    const uint32_t hard  = (gather4((w.x | ~tx) & 0x80808080U) << 4) | gather4((w.y | ~ty) & 0x80808080U);
-    const uint32_t zeros = (gather4(~(w.x | tx) & 0x80808080U) << 4) | gather4(~(w.y | ty) & 0x80808080U);
-    zero                 = zero || (zeros & keep) != 0;
-    hb[b]                = static_cast<uint8_t>(hard & keep);
-  }
-  if (__builtin_amdgcn_ballot_w64(zero) != 0 && (threadIdx.x & 63) == 0) {
-    *reinterpret_cast<volatile uint32_t*>(s_flag) = token;
-  }
-  __syncthreads();
-  return *reinterpret_cast<volatile uint32_t*>(s_flag) != token;
-}
-
-/* Check-to-variable storage. c2v is kept per edge, as the reference keeps it (ldpc_decoder_impl.h:224-226), but
- * only for the edges that exist: int8 c2v[e][t] for graph edge e and lifted check node t (edge-major, stride Z, so
- * a wave's 64 consecutive check nodes read 64 consecutive bytes). BG1 Z=384: 316 * 384 = 121,344 B. An all-zero c2v
- * is the "not yet initialised" state: soft (-) 0 = soft, the first-iteration copy of
- * update_variable_to_check_messages (impl.cpp:196-200).
- *
- * Soft bits inside the decoder hold [-120, 120] for finite LLRs and +-121 for +-infinity (the reference's +-127,
- * llr.h:238): with infinity one step above the finite range, "promotion_sum overflows to infinity" is a single
- * clamp to +-121 and x = s - clamp(s, +-120) is the infinity indicator (+-1 or 0). Only the sign and the zero test of
- * a soft bit ever leave the decoder (hard_decision), and both are unchanged by the encoding. */
-
-/* scale_llr (ldpc_decoder_generic.cpp:70-79) for a finite magnitude m in [0, 120]: round(float(m) * sf), half away
- * from zero. v_mul_f32 is correctly rounded and llvm.round is exact, so this equals the host std::round. */
-template <bool SF08>
-__device__ __forceinline__ int scale_mag(int m, float sf)
-{
-  if (SF08) {
-    /* sf = 0.8f (the PHY default, ldpc_decoder.h:50): round(0.8 m) = floor((4m + 2) / 5) = (52432 m + 26216) >> 16
-     * for m in [0, 120] (checked exhaustively against the float formula) */
-    return static_cast<int>((__umul24(static_cast<uint32_t>(m), 52432U) + 26216U) >> 16);
-  }
-  return static_cast<int>(__builtin_roundf(static_cast<float>(m) * sf));
-}
-
-__device__ __forceinline__ int med3i(int x, int lo, int hi) { return min(max(x, lo), hi); } /* v_med3_i32 */
-
-/* Four int8 LLRs with +-127 (infinity) mapped to the decoder-internal +-121. */
-__device__ __forceinline__ uint32_t clamp_inf4(uint32_t w)
-{
-  uint32_t r = 0;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int v = med3i(__builtin_amdgcn_sbfe(static_cast<int>(w), 8 * b, 8), -LLR_INTERNAL_INF, LLR_INTERNAL_INF);
-    r |= (static_cast<uint32_t>(v) & 0xffU) << (8 * b);
-  }
-  return r;
-}
-
-#if defined(LDPC_HIP_DIAG) || defined(LDPC_HIP_DIAG_PHASE) || defined(LDPC_HIP_DIAG_TBJ) || defined(LDPC_HIP_DIAG_DM)
-} // namespace
-/* diagnostic build only: s_memtime stamps of block 0 after every step barrier */
-static __device__ uint64_t g_diag[4096];
-static __device__ uint64_t g_diag2[64 * 16 * 8]; /* last iteration: per step and wave, (start, end of row work) or phases */
-namespace {
-#endif
-#ifdef LDPC_HIP_DIAG /* specialised kernel: per (step, wave) phase stamps of block 0, overwritten every iteration */
-#define SPEC_STAMP(S, k)                                                                                               \
-  do {                                                                                                                 \
-    if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) {                                                                  \
-      g_diag2[((S) * 16 + (threadIdx.x >> 6)) * 8 + (k)] = __builtin_amdgcn_s_memtime();                               \
-    }                                                                                                                  \
-  } while (0)
-#else
-#define SPEC_STAMP(S, k) ((void)0)
-#endif
-#if defined(LDPC_HIP_DIAG) && defined(LDPC_HIP_DIAG_FULL) /* phase stamps inside a step: perturb the schedule */
-#define SPEC_STAMP_FULL(S, k) SPEC_STAMP(S, k)
-#else
-#define SPEC_STAMP_FULL(S, k) ((void)0)
-#endif
-#ifdef LDPC_HIP_DIAG_PHASE /* diagnostic build: s_memtime at phase boundaries of the row update */
-#define PHASE(i) (ph[(i)] = __builtin_amdgcn_s_memtime())
-#else
-#define PHASE(i) ((void)0)
-#endif
-
-/* Partner lane (lane ^ 32) value through v_permlane32_swap. */
-__device__ __forceinline__ uint32_t partner32(uint32_t v, int half)
-{
-  const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-  return half ? r[0] : r[1];
-}
-
-/* LDS byte at an absolute LDS address. The decode kernel has no static LDS, so its dynamic LDS (smem) starts at LDS
- * address 0 and the soft bits (lay.soft == 0) are addressed by column offset alone -- checked once per launch. */
-typedef __attribute__((address_space(3))) int8_t lds_i8;
-__device__ __forceinline__ lds_i8* lds_byte(uint32_t addr) { return (lds_i8*)(uintptr_t)addr; }
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-__device__ __forceinline__ lds_u32* lds_word(uint32_t addr) { return (lds_u32*)(uintptr_t)addr; }
-
-/* ---- per-edge and per-row arithmetic shared by the generic and the specialised row updates (see row_update) ---- */
-
-/* v2c = soft (-) c2v with the infinity push: med3(s - c, +-120) + 512 x, x = s - med3(s, +-120). */
-__device__ __forceinline__ int v2c_of(int s, int c)
-{
-  const int x = s - med3i(s, -LLR_MAX, LLR_MAX); /* infinity indicator: +-1 or 0 */
-  return (x << 9) + med3i(s - c, -LLR_MAX, LLR_MAX); /* v_lshl_add_u32 */
-}
-
-/* Two-minimum scan step: m2 = min(m2, max(m1, a)) as one v_med3_u32 (the compiler otherwise emits max + min). */
-__device__ __forceinline__ void scan_edge(uint32_t& m1, uint32_t& m2, int a)
-{
-  asm("v_med3_u32 %0, %1, %2, %3" : "=v"(m2) : "v"(m1), "v"(a), "v"(m2));
-  m1 = min(m1, static_cast<uint32_t>(a));
-}
-
-/* End of pass 1: merge a split row's halves (P = 2), then the two scaled magnitudes with the parity sign folded in:
- * p1 for edges with |v2c| != min, p2 for |v2c| == min (see row_update). m1 is returned merged. */
-template <int P, bool SF08>
-__device__ __forceinline__ void row_scale(uint32_t& m1, uint32_t m2, uint32_t sx, int half, float sf, int& p1, int& p2)
-{
-  if (P == 2) {
-    const uint32_t oth = partner32(m1 | (m2 << 8), half);
-    const uint32_t o1 = oth & 0xffU, o2 = oth >> 8;
-    m2                = min(min(m2, o2), max(m1, o1));
-    m1                = min(m1, o1);
-    sx ^= partner32(sx, half);
-  }
-  const int n1  = scale_mag<SF08>(static_cast<int>(m1), sf);
-  const int n2  = scale_mag<SF08>(static_cast<int>(m2), sf);
-  const int neg = static_cast<int>(sx) >> 31;
-  p1            = (n1 ^ neg) - neg;
-  p2            = (n2 ^ neg) - neg;
-  /* opaque to the optimiser: otherwise it sinks the scaling into every edge as select + rescale */
-  asm volatile("" : "+v"(p1), "+v"(p2));
-}
-
-/* Sign mask (0 / -1) and magnitude of v2c. The mask stays opaque, so the magnitude is v_xor + v_sub (not the abs
- * idiom's v_sub + v_max) and pass 2 reuses the mask instead of shifting again. */
-__device__ __forceinline__ int sign_mask(int v)
-{
-  int sv = v >> 31;
-  asm("" : "+v"(sv));
-  return sv;
-}
-
-/* c2v' of an edge with v2c sign mask sv and |v2c| a. */
-__device__ __forceinline__ int c2v_new(int sv, int a, uint32_t m1, int p1, int p2)
-{
-  const int ms = (a == static_cast<int>(m1)) ? p2 : p1;
-  return (ms ^ sv) - sv;
-}
-
-/* soft' = promotion_sum(c2v', v2c). */
-__device__ __forceinline__ int soft_new(int c, int v) { return med3i(c + v, -LLR_INTERNAL_INF, LLR_INTERNAL_INF); }
-
-/* One lifted check node t of a row of degree D -- update_variable_to_check_messages,
- * update_check_to_variable_messages and update_soft_bits (ldpc_decoder_impl.cpp:176-308) restricted to Z-lane t,
- * with the generic kernels' arithmetic (ldpc_decoder_generic.cpp:30-120).
- *
- * P = 1: one lane owns the check node and scans all D edges in order.
- * P = 2: lanes l and l ^ 32 share the check node; the lower half scans edges [0, D0), the upper half [D0, D), and
- *        the partial (min1, min2, sign parity) are merged across the pair: min1 = min(A, B), min2 = min(min2_A,
- *        min2_B, max(min1_A, min1_B)) -- the two smallest of the multiset, as the sequential scan finds them.
- * Edge words (shift | col * Z << 16) come from the LDS edge table; the upper half's slot starts at edge D0.
- *
- * LLR special cases with the internal encoding above (c2v is never infinite: |c2v| <= round(120 sf) <= 120):
- *   v2c   = isinf(s) ? s : clamp(s - c2v, +-120)           (llr.cpp:56-71 operator-)
- *           computed as clamp(s - c2v, +-120) + 512 x: an infinite v2c keeps its sign and a magnitude above 512,
- *           which the two-minimum scan treats exactly like the reference's +-127 (min and min2 start at 120 and
- *           only a magnitude strictly below them is taken; |v2c| == min never holds for it);
- *   soft' = promotion_sum(c2v', v2c) = clamp(c2v' + v2c, +-121)   (llr.cpp:73-86): a finite sum saturates to
- *           infinity past +-120, and an infinite v2c (|v2c| > 512 > 121 + |c2v'|) stays infinite. */
-template <int D, int P, bool SF08>
-__device__ __forceinline__ void row_update(int t, int half, const uint32_t* s_slot, int8_t* s_soft,
-                                           int8_t* s_c2v_row, float sf, int Z, int trash, uint64_t* ph)
-{
-  PHASE(0);
-  constexpr int DP = (P == 1) ? D : (D + 1) / 2; /* edges scanned by this lane */
-  constexpr int D0 = DP;                         /* first edge of the upper half (P = 2) */
-  const int     kb = (P == 2 && half) ? D0 : 0;
-  int8_t*       cq = s_c2v_row + t + kb * Z;     /* this lane's c2v of local edge kk: cq + kk * Z */
-
-  lds_i8* sp[DP]; /* soft bit of edge kk at the cyclic shift */
-  int8_t* cp[DP]; /* c2v of edge kk */
-  int     vc[DP]; /* v2c */
-#pragma unroll
-  for (int kk = 0; kk < DP; ++kk) {
-    /* edge word shift | col * Z << 16 (wave-uniform, step_task); with splitting the two halves select per lane */
-    const bool dummy = (P == 2 && D0 + kk >= D && half); /* upper half of an odd-degree row has one edge less */
-    const uint32_t ew   = s_slot[kk];   /* this lane's edge (the upper half's slot starts at edge D0) */
-    const uint32_t sh   = ew & 0xffffU;
-    const uint32_t colz = ew >> 16;
-    const uint32_t j0   = static_cast<uint32_t>(t) + sh;
-    const uint32_t j    = min(j0, j0 - static_cast<uint32_t>(Z)); /* (t + shift) mod Z */
-    sp[kk]              = lds_byte(colz + j); /* a dummy edge points at the scratch bytes */
-    cp[kk]              = dummy ? s_soft + trash : cq;
-    cq += Z; /* incremental: keeps the c2v addresses single VOP2 adds */
-  }
-  PHASE(1);
-  int      av[DP];                     /* |v2c| */
-  int      sg[DP];                     /* sign mask of v2c */
-  uint32_t m1 = LLR_MAX, m2 = LLR_MAX; /* the reference's min and min2 (gen.cpp:46-68) */
-  uint32_t sx = 0;                     /* sign parity of all v2c (bit 31) */
-#pragma unroll
-  for (int kk = 0; kk < DP; ++kk) {
-    const bool dummy = (P == 2 && D0 + kk >= D && half);
-    const int  v     = v2c_of(*sp[kk], *cp[kk]);
-    vc[kk]           = v;
-    const int sv     = sign_mask(v);
-    sg[kk]           = sv;
-    const int a      = dummy ? 0xfff : (v ^ sv) - sv;
-    av[kk]           = a;
-    scan_edge(m1, m2, a);
-    sx ^= dummy ? 0U : static_cast<uint32_t>(v);
-  }
-  PHASE(2);
-  /* c2v' of edge k = sign(v2c_k) * sign(parity) * (k == idx ? n2 : n1) (gen.cpp:93-105). The reference's idx is
-   * the first edge with |v2c| == min; any other edge with |v2c| == min makes min2 == min, so "k == idx" can be
-   * replaced by "|v2c_k| == min" without changing a single output, and no edge index is tracked. The parity's sign
-   * is folded into the two magnitudes once per row. */
-  int p1, p2;
-  row_scale<P, SF08>(m1, m2, sx, half, sf, p1, p2);
-  PHASE(3);
-#pragma unroll
-  for (int kk = 0; kk < DP; ++kk) {
-    const int c = c2v_new(sg[kk], av[kk], m1, p1, p2);
-    *cp[kk]     = static_cast<int8_t>(c);
-    *sp[kk]     = static_cast<int8_t>(soft_new(c, vc[kk]));
-  }
-  PHASE(4);
-}
-
-/* Dispatch on the (wave-uniform) row degree. BG1 degrees: 3..10, 19; BG2: 3..10 (ldpc_luts_impl.cpp:4383-4519). */
-template <int P, bool SF08>
-__device__ __forceinline__ void row_dispatch(int deg, int t, int half, const uint32_t* s_slot, int8_t* s_soft,
-                                             int8_t* c2v_row, float sf, int Z, int trash, uint64_t* ph)
-{
-  switch (deg) {
-    case 3: row_update<3, P, SF08>(t, half, s_slot, s_soft, c2v_row, sf, Z, trash, ph); break;
-    case 4: row_update<4, P, SF08>(t, half, s_slot, s_soft, c2v_row, sf, Z, trash, ph); break;
-    case 5: row_update<5, P, SF08>(t, half, s_slot, s_soft, c2v_row, sf, Z, trash, ph); break;
-    case 6: row_update<6, P, SF08>(t, half, s_slot, s_soft, c2v_row, sf, Z, trash, ph); break;
-    case 7: row_update<7, P, SF08>(t, half, s_slot, s_soft, c2v_row, sf, Z, trash, ph); break;
-    case 8: row_update<8, P, SF08>(t, half, s_slot, s_soft, c2v_row, sf, Z, trash, ph); break;
-    case 9: row_update<9, P, SF08>(t, half, s_slot, s_soft, c2v_row, sf, Z, trash, ph); break;
-    case 10: row_update<10, P, SF08>(t, half, s_slot, s_soft, c2v_row, sf, Z, trash, ph); break;
-    default: row_update<19, P, SF08>(t, half, s_slot, s_soft, c2v_row, sf, Z, trash, ph); break;
-  }
-}
 
 /* ---- specialised decoder: the whole iteration unrolled at compile time (ldpc_spec.h) ---------------------------
  * The step sequence and every row's degree, columns and shifts are constants, so a row needs no table reads, no
@@ -1391,820 +978,4 @@ struct qdec {
 } // namespace sp
 
 } // namespace
-
-/* Lifted graphs of every (BG, Z), indexed by slot = (BG - 1) * 51 + lifting position; slot 102 + s holds graph s
- * with the narrow step schedule (ldpc_graph.h NARROW_SLOT_BASE). Constant memory: all row, step and edge words are
- * read with scalar loads (the row a wave works on is uniform). One copy per translation unit (static): the one
- * ldpc_hip_kernels.hip uploads serves the generic and mixed kernels; the specialised kernels compiled elsewhere
- * (ldpc_spec_kernels_*.hip) take every graph field from their compile-time schedule and never read it. */
-static __constant__ graph_desc c_graphs[204];
-
-} // namespace ldpc_hip
-#include "ldpc_dematch_body.h" /* dematch_body: the decode kernels' fused first phase */
-namespace ldpc_hip {
-
-/* Graph fields of the generic body (this unit's c_graphs). */
-__device__ __forceinline__ int graph_field_Z(int slot) { return c_graphs[slot].Z; }
-__device__ __forceinline__ int graph_field_K(int slot) { return c_graphs[slot].K; }
-__device__ __forceinline__ int graph_field_N(int slot) { return c_graphs[slot].N_full; }
-__device__ __forceinline__ int graph_field_task_waves(int slot) { return c_graphs[slot].task_waves; }
-
-/* One codeblock per workgroup (the body of ldpc_decode_kernel and ldpc_decode_mixed_kernel). The generic body also
- * runs in workgroups wider than its schedule (mixed launches): waves at or beyond graph->task_waves only take part in
- * the block-wide phases and the step barriers. */
-template <bool SF08, int SPEC_ID>
-__device__ __forceinline__ void decode_cb(const dec_cb& d, int graph_slot, const step_task* __restrict__ tasks,
-                                          const lds_layout& lay, const int8_t* llr_base,
-                                          uint8_t* __restrict__ out_base, ldpc_hip_cb_result* __restrict__ res_base,
-                                          const uint32_t* __restrict__ crc_tables, const dematch_cb* dm_cbs,
-                                          const dematch_cb& dm_one)
-{
-#define graph (&c_graphs[graph_slot])
-  constexpr bool SPEC = SPEC_ID >= 0; /* specialised body: spec::k_specs[SPEC_ID] */
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  int8_t*   s_soft = reinterpret_cast<int8_t*>(smem); /* lay.soft == 0: column offsets are LDS addresses */
-  if (static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_i8*)s_soft)) != 0U || lay.soft != 0U) {
-    __builtin_trap(); /* lds_byte() would address the wrong bytes */
-  }
-  int8_t*   s_c2v  = reinterpret_cast<int8_t*>(smem + lay.c2v);
-  uint8_t*  s_hb   = smem + lay.hard;
-  uint32_t* s_red  = reinterpret_cast<uint32_t*>(smem + lay.red);
-  uint32_t* s_crct = reinterpret_cast<uint32_t*>(smem + lay.crct);
-
-#ifdef LDPC_HIP_DIAG_CB /* diagnostic build: stamp 6, the body's entry (before a fused dematcher) */
-  if (threadIdx.x == 0 && blockIdx.x < 1024) {
-    reinterpret_cast<uint64_t*>(const_cast<uint32_t*>(crc_tables) + DIAG_CB_OFFSET)[blockIdx.x * 8 + 6] =
-        __builtin_amdgcn_s_memrealtime();
-  }
-#endif
-  if (dm_cbs != nullptr || dm_one.soft != nullptr) {
-    /* fused rate dematching (ldpc_hip_dematch_decode_launch, the HAL batch): this CB's dematcher runs first, into the
-     * soft buffer the prologue then loads (llr_base + d.llr_offset); its LDS staging and table copy sit in the
-     * decoder's dynamic LDS (the launch reserves DM_FUSED_LDS), free again after the barrier. A workgroup's own
-     * global stores are visible to its loads after the barrier. */
-    dematch_body(dm_cbs != nullptr ? dm_cbs[blockIdx.x] : dm_one,
-                 *reinterpret_cast<const demod_tables*>(crc_tables + DTAB_OFFSET), reinterpret_cast<int8_t*>(smem),
-                 *reinterpret_cast<demod_tables*>(smem + DM_STAGE));
-    __syncthreads();
-  }
-  if (d.keep_passed != 0 && res_base != nullptr && res_base[d.result_index].crc_pass != 0) {
-    return; /* HARQ: CRC passed in an earlier transmission; message and result stay (pusch_decoder_impl.cpp:336-346) */
-  }
-  const int     tid    = threadIdx.x;
-  const int     nthr   = blockDim.x;
-  const int     lane   = tid & 63;
-  const int     wave   = __builtin_amdgcn_readfirstlane(tid >> 6);
-  /* the specialised bodies take every graph field from their compile-time schedule: they may be compiled in a unit
-   * whose c_graphs copy is never uploaded (ldpc_spec_kernels_*.hip) */
-  using SG             = spec::spec_graph<SPEC ? SPEC_ID : 0>;
-  const int     Z      = SPEC ? SG::g.Z : graph_field_Z(graph_slot);
-  const int     K      = SPEC ? SG::g.K : graph_field_K(graph_slot);
-  const int     N_full = SPEC ? SG::g.N_full : graph_field_N(graph_slot);
-  const int     KZ     = K * Z;
-  const int     L      = static_cast<int>(d.llr_length);
-  const int8_t* llr    = llr_base + d.llr_offset;
-  uint8_t*      out    = out_base + d.out_offset;
-  const float   sf     = d.scaling_factor;
-
-#ifdef LDPC_HIP_DIAG_CB_DM
-#define LDPC_DIAG_CB_DM_ON 1
-#else
-#define LDPC_DIAG_CB_DM_ON 0
-#endif
-#ifdef LDPC_HIP_DIAG_CB /* diagnostic build: device-wide 100 MHz stamps per workgroup, in the context's table buffer
-                          * (every translation unit's kernels reach it; ldpc_hip_diag_cb_read); with
-                          * LDPC_HIP_DIAG_CB_DM slots 1-3 hold the fused dematcher's stamps instead */
-#define CB_STAMP(k)                                                                                                    \
-  if (tid == 0 && blockIdx.x < 1024 && !(LDPC_DIAG_CB_DM_ON && (k) >= 1 && (k) <= 3)) {                              \
-    reinterpret_cast<uint64_t*>(const_cast<uint32_t*>(crc_tables) + DIAG_CB_OFFSET)[blockIdx.x * 8 + (k)] =         \
-        __builtin_amdgcn_s_memrealtime();                                                                              \
-  }
-#else
-#define CB_STAMP(k)
-#endif
-  CB_STAMP(0);
-  /* ---- prologue: soft bits (load_soft_bits, impl.cpp:149-174), CRC tables, zeroed c2v records ----
-   * Every global load a thread needs is issued before any of them is used (the LLRs, up to PRO_U 16-byte loads per
-   * thread and pass, then the CRC tables), so their latencies overlap instead of adding up loop trip by loop trip;
-   * the last non-zero LLR index is reduced per wave (DPP) into s_red[wave], so no barrier is needed before it. */
-  int       last_local = 0;
-  const int total      = N_full * Z;
-  const bool vec16     = (reinterpret_cast<uintptr_t>(llr) & 15U) == 0 && ((2 * Z) & 15) == 0 && (L & 15) == 0;
-  constexpr int PRO_U  = 4;
-  const int z4 = (2 * Z) / 16, l4 = L / 16, t4 = (total + 15) / 16;
-  const uint4* g4 = reinterpret_cast<const uint4*>(llr);
-  uint4        pv[PRO_U];
-  int          base4 = 0;
-  if (vec16) { /* first pass's loads: [0, 2Z) zero, [2Z, 2Z + L) LLRs, rest zero */
-#pragma unroll
-    for (int u = 0; u < PRO_U; ++u) {
-      const int i = tid + u * nthr;
-      pv[u]       = (i >= z4 && i < z4 + l4 && i < t4) ? g4[i - z4] : make_uint4(0, 0, 0, 0);
-    }
-  }
-  /* BG1 split-row address table (specialised kernel): the context's global copy, 16 bytes per load, its loads in
-   * flight with the LLRs'; stored into the c2v region before the prologue barrier (a thread writes other lanes' words) */
-  using SD                = sp::dec<SG::g>;
-  /* one-wave graphs: the lane-split decoder (sp::qdec); its address table comes into registers here, its loads in
-   * flight with the LLRs' (the same words for every codeblock of a launch: L2-resident after the first) */
-  constexpr bool QUAD     = SPEC && spec::is_quad(SG::g);
-  constexpr int  QN       = QUAD ? SG::q.slots : 1;
-  using QD                = sp::qdec<SG::g, SG::q>;
-  uint32_t      qtab[QN];
-  if constexpr (QUAD) {
-    const uint32_t* gq = crc_tables + lay.split_tab;
-#pragma unroll
-    for (int q = 0; q < QN; ++q) {
-      qtab[q] = gq[static_cast<uint32_t>(q) * QD::WG + static_cast<uint32_t>(tid)];
-    }
-  }
-  constexpr int SPLIT_U4  = (SPEC && !QUAD) ? SD::LDS_PAIRS * static_cast<int>(SD::WG) / 4 : 0;
-  constexpr int SPLIT_PER = 5; /* loads per thread: LDS_PAIRS / 4 at the decoder's own width */
-  uint4         stv[SPLIT_PER];
-  if constexpr (SPLIT_U4 > 0) {
-    const uint4* gs = reinterpret_cast<const uint4*>(crc_tables + lay.split_tab);
-#pragma unroll
-    for (int u = 0; u < SPLIT_PER; ++u) {
-      const int i = tid + u * nthr;
-      stv[u]      = i < SPLIT_U4 ? gs[i] : make_uint4(0, 0, 0, 0);
-    }
-  }
-  /* CRC tables for the LDS copy (T_0, T_1..T_3, x^(32 e) mod G: 324 16-byte chunks, every source 16-byte aligned):
-   * issued here with the LLRs' and the split table's loads, stored after the LLRs. Round 4 had a loop of two 4-byte
-   * loads per trip before the LLR loads: five dependent trips in a 128-thread workgroup (BG2 Z=36), most of its
-   * 5 us prologue on the work-queue path. */
-  constexpr int   CRC_U4  = CRC_LDS_WORDS / 4;
-  constexpr int   CRC_PER = 3; /* loads per thread in flight: every chunk at 108 threads or more */
-  static_assert(CRC_LDS_WORDS % 4 == 0 && 256 % 4 == 0 && CRC_TABLE_SIZE % 4 == 0 && CRC_SLICE_OFFSET % 4 == 0 &&
-                    CRC_SLICE_WORDS % 4 == 0,
-                "CRC tables copied in 16-byte chunks");
-  const bool      crc_on = d.crc_mode != LDPC_HIP_CRC_MODE_NONE;
-  const uint4*    tab4   = reinterpret_cast<const uint4*>(crc_tables + static_cast<int>(d.crc_poly) * CRC_TABLE_SIZE);
-  const uint4*    slc4 =
-      reinterpret_cast<const uint4*>(crc_tables + CRC_SLICE_OFFSET + static_cast<int>(d.crc_poly) * CRC_SLICE_WORDS);
-  auto crc_chunk = [&](int j) { return j < 64 ? tab4[j] : (j < 256 ? slc4[j - 64] : tab4[j - 192]); };
-  uint4 crcv[CRC_PER];
-  if (crc_on) {
-#pragma unroll
-    for (int u = 0; u < CRC_PER; ++u) {
-      const int j = tid + u * nthr;
-      crcv[u]     = j < CRC_U4 ? crc_chunk(j) : make_uint4(0, 0, 0, 0);
-    }
-  }
-  {
-    uint4*    c2v4 = reinterpret_cast<uint4*>(s_c2v);
-    int       n16  = 0; /* specialised: c2v in registers */
-    if constexpr (!SPEC) {
-      n16 = (static_cast<int>(graph->c2v_bytes) + 15) / 16;
-    }
-    for (int i = tid; i < n16; i += nthr) {
-      c2v4[i] = make_uint4(0, 0, 0, 0);
-    }
-    const int nhb = static_cast<int>(lay.red - lay.hard) / 4;
-    for (int i = tid; i < nhb; i += nthr) {
-      reinterpret_cast<uint32_t*>(s_hb)[i] = 0;
-    }
-  }
-  if constexpr (SPEC) {
-    /* dummy edges of odd split rows read and write a scratch column held at +infinity (+121): never a minimum, no
-     * sign, and promotion_sum keeps it there (namespace sp) */
-    const int n4 = (static_cast<int>(lay.soft_stride) + 3) / 4; /* whole column (the layout leaves 64 bytes of slack) */
-    int*      sc = reinterpret_cast<int*>(s_soft + static_cast<int>(lay.soft_stride) * N_full);
-    for (int i = tid; i < n4; i += nthr) {
-      sc[i] = 0x79797979; /* 121 = 0x79 in every byte */
-    }
-  } else {
-    /* edge table: per row EDGE_SLOT words shift | (col * Z) << 16, padded with dummy edges at the scratch bytes after
-     * the soft columns */
-    uint32_t*      s_edges = reinterpret_cast<uint32_t*>(smem + lay.edges);
-    const uint32_t dummy   = static_cast<uint32_t>(graph->N_full) * graph->Z << 16;
-    for (int i = tid; i < graph->M * EDGE_SLOT; i += nthr) {
-      const int      r   = i / EDGE_SLOT, k = i - r * EDGE_SLOT;
-      const uint32_t rw  = graph->rows[r];
-      uint32_t       w   = dummy;
-      if (k < static_cast<int>(rw >> 16)) {
-        const uint32_t ew = graph->edges[(rw & 0xffffU) + k];
-        w = (ew >> 16) | ((ew & 0xffffU) << 16);
-      }
-      s_edges[i] = w;
-    }
-  }
-  if (tid == 0) {
-    s_red[30] = 0; /* block_hard_decision's flag */
-  }
-  if constexpr (SPLIT_U4 > 0) {
-    uint4*       st = reinterpret_cast<uint4*>(smem + lay.c2v);
-    const uint4* gs = reinterpret_cast<const uint4*>(crc_tables + lay.split_tab);
-#pragma unroll
-    for (int u = 0; u < SPLIT_PER; ++u) {
-      const int i = tid + u * nthr;
-      if (i < SPLIT_U4) {
-        st[i] = stv[u];
-      }
-    }
-    for (int i = tid + SPLIT_PER * nthr; i < SPLIT_U4; i += nthr) { /* narrower workgroups only */
-      st[i] = gs[i];
-    }
-  }
-  if (vec16) {
-    uint4* s4 = reinterpret_cast<uint4*>(s_soft);
-    while (true) {
-#pragma unroll
-      for (int u = 0; u < PRO_U; ++u) {
-        const int i = base4 + tid + u * nthr;
-        if (i >= t4) {
-          continue;
-        }
-        uint4 v = pv[u];
-        if (i >= z4 && i < z4 + l4) {
-          const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int q = 3; q >= 0; --q) {
-            if (wv[q] != 0) {
-              const int hi = 31 - __builtin_clz(wv[q]); /* highest set bit -> byte index */
-              last_local   = max(last_local, (i - z4) * 16 + q * 4 + hi / 8 + 1);
-              break;
-            }
-          }
-          v = make_uint4(clamp_inf4(v.x), clamp_inf4(v.y), clamp_inf4(v.z), clamp_inf4(v.w));
-        }
-        s4[i] = v;
-      }
-      base4 += PRO_U * nthr;
-      if (base4 >= t4) {
-        break;
-      }
-#pragma unroll
-      for (int u = 0; u < PRO_U; ++u) { /* the next pass's loads (blocks narrower than t4 / PRO_U threads) */
-        const int i = base4 + tid + u * nthr;
-        pv[u]       = (i >= z4 && i < z4 + l4 && i < t4) ? g4[i - z4] : make_uint4(0, 0, 0, 0);
-      }
-    }
-  } else if ((reinterpret_cast<uintptr_t>(llr) & 15U) == 0) {
-    /* 16-byte loads whatever the alignment of 2Z and L (Z % 8 != 0, e.g. BG2 Z=36, or shortened lengths): the chunks
-     * land at soft + 2Z + 16 k through 4-byte (Z even) or 2-byte LDS writes, the last L % 16 LLRs by byte loads, and
-     * a thread issues all its loads of a pass (and the tail's) before storing any. A loop of byte loads instead paid
-     * one memory round trip per trip (BG2 Z=36, 128 threads: 15 trips, a 22 us prologue from pinned host memory). */
-    const int lc = L >> 4, lt = L & 15;
-    int8_t    tv = 0;
-    if (tid < lt) {
-      tv = llr[16 * lc + tid];
-    }
-    for (int i = tid; i < 2 * Z; i += nthr) {
-      s_soft[i] = 0;
-    }
-    for (int i = 2 * Z + L + tid; i < total; i += nthr) {
-      s_soft[i] = 0;
-    }
-    for (int c0 = 0; c0 < lc; c0 += PRO_U * nthr) {
-      uint4 w[PRO_U];
-#pragma unroll
-      for (int u = 0; u < PRO_U; ++u) {
-        const int k = c0 + tid + u * nthr;
-        w[u]        = k < lc ? g4[k] : make_uint4(0, 0, 0, 0);
-      }
-#pragma unroll
-      for (int u = 0; u < PRO_U; ++u) {
-        const int k = c0 + tid + u * nthr;
-        if (k >= lc) {
-          continue;
-        }
-        const uint32_t wv[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
-#pragma unroll
-        for (int q = 3; q >= 0; --q) {
-          if (wv[q] != 0) {
-            const int hi = 31 - __builtin_clz(wv[q]);
-            last_local   = max(last_local, k * 16 + q * 4 + hi / 8 + 1);
-            break;
-          }
-        }
-        int8_t* dst = s_soft + 2 * Z + 16 * k;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const uint32_t c = clamp_inf4(wv[q]);
-          if ((Z & 1) == 0) {
-            reinterpret_cast<uint32_t*>(dst)[q] = c;
-          } else {
-            reinterpret_cast<uint16_t*>(dst)[2 * q]     = static_cast<uint16_t>(c);
-            reinterpret_cast<uint16_t*>(dst)[2 * q + 1] = static_cast<uint16_t>(c >> 16);
-          }
-        }
-      }
-    }
-    if (tid < lt) {
-      const int li = 16 * lc + tid;
-      if (tv != 0) {
-        last_local = max(last_local, li + 1);
-      }
-      s_soft[2 * Z + li] = static_cast<int8_t>(med3i(tv, -LLR_INTERNAL_INF, LLR_INTERNAL_INF));
-    }
-  } else {
-    for (int i = tid; i < total; i += nthr) {
-      int8_t    v  = 0;
-      const int li = i - 2 * Z;
-      if (li >= 0 && li < L) {
-        v = llr[li];
-        if (v != 0) {
-          last_local = max(last_local, li + 1);
-        }
-        v = static_cast<int8_t>(med3i(v, -LLR_INTERNAL_INF, LLR_INTERNAL_INF));
-      }
-      s_soft[i] = v;
-    }
-  }
-  CB_STAMP(7); /* diagnostic build: the soft bits' loads have returned and are stored */
-  if (crc_on) {
-    uint4* s4 = reinterpret_cast<uint4*>(s_crct);
-#pragma unroll
-    for (int u = 0; u < CRC_PER; ++u) {
-      const int j = tid + u * nthr;
-      if (j < CRC_U4) {
-        s4[j] = crcv[u];
-      }
-    }
-    for (int j = tid + CRC_PER * nthr; j < CRC_U4; j += nthr) { /* workgroups of fewer than 108 threads */
-      s4[j] = crc_chunk(j);
-    }
-  }
-  {
-    const int wl = wave_max(last_local);
-    if (lane == 0) {
-      s_red[wave] = static_cast<uint32_t>(wl);
-    }
-  }
-  __syncthreads();
-  CB_STAMP(1);
-  /* lane i reads wave i's maximum (one LDS read per lane), then a wave maximum: uniform */
-  const int last = wave_max(lane < (nthr + 63) / 64 ? static_cast<int>(s_red[lane]) : 0);
-  const int nb   = (KZ + 7) / 8;
-  const int Lsig = KZ - static_cast<int>(d.nof_filler_bits);
-
-  int  has_value  = 0;
-  int  iterations = d.max_iterations;
-  bool write_out  = true;
-
-  if (last == 0) {
-    /* All-zero LLRs (impl.cpp:86-94): no CRC -> message of ones; with a CRC -> untouched, nullopt. */
-    if (d.crc_mode == LDPC_HIP_CRC_MODE_EARLY_STOP) {
-      write_out = false;
-    } else {
-      for (int b = tid; b < nb; b += nthr) {
-        const int nbits = min(8, KZ - 8 * b);
-        s_hb[b]         = static_cast<uint8_t>((0xff00U >> nbits) & 0xffU);
-      }
-      __syncthreads();
-      if (d.crc_mode == LDPC_HIP_CRC_MODE_CHECK_AFTER) {
-        has_value = (block_crc(s_hb, Lsig, d.crc_poly, s_crct,
-                               s_red, crc_tables + CRC_MCOL_OFFSET + d.crc_poly * CRC_MCOL_WORDS) == 0);
-      }
-    }
-  } else {
-    /* Codeblock length and number of layers (impl.cpp:103-114). */
-    int cb_len = max(last + 2 * Z, (K + 4) * Z);
-    cb_len     = ((cb_len + Z - 1) / Z) * Z;
-    const int nof_layers = cb_len / Z - K;
-    const int half  = lane >> 5;
-    const int trash = N_full * Z; /* scratch bytes after the soft bits take the dummy-edge stores */
-    /* steps whose first row is a layer beyond nof_layers are skipped; a step's own rows are checked per task */
-    int n_steps = 0; /* generic body only */
-    if constexpr (!SPEC) {
-      n_steps = graph->n_steps;
-      for (int s = 0; s < n_steps; ++s) {
-        if (graph->step_row0[s] >= nof_layers) {
-          n_steps = s;
-          break;
-        }
-      }
-    }
-    /* This wave's task of step s is the step_task at tasks[s * tw + wave]. It is fetched one step ahead, lane i
-     * loading word i (a vector load, so the step barrier does not wait for it), and read out with v_readlane. */
-    const int        tw   = SPEC ? 1 : graph_field_task_waves(graph_slot);
-    const bool       idle = wave >= tw; /* wider workgroup than the schedule (mixed launch): barriers only */
-    const step_task* tk   = tasks + (idle ? 0 : wave); /* this wave's task of step s: tk[s * tw] (scalar loads) */
-
-    bool     hb_current = false;
-#ifdef LDPC_HIP_DIAG
-    int diag_n = 1;
-    if (blockIdx.x == 0 && tid == 0) {
-      g_diag[0] = __builtin_amdgcn_s_memtime();
-    }
-#endif
-    step_task nxt = tk[0]; /* fetched one step ahead: the scalar load overlaps the previous step's row update */
-    typename SD::cr_t cr; /* specialised kernel: this lane's c2v bytes, all zero = not yet initialised */
-    for (auto& q : cr) {
-      q = 0;
-    }
-    sp::lanes sl{};
-    if constexpr (!QUAD) {
-      sl = SD::make_lanes(wave, lane, __builtin_amdgcn_readfirstlane(nof_layers),
-                                        lay.c2v + 4U * static_cast<uint32_t>(tid));
-    }
-    typename SD::pf_t pf = {0, 0, 0, 0, 0};
-    if constexpr (SPEC && !QUAD) {
-      SD::template load_pf<0>(pf, sl);
-      SD::ext_init(cr, sl); /* the extension edges kept in registers: their state from the soft bits, once */
-    }
-    uint32_t qcr[QN]; /* lane-split decoder: this lane's c2v pairs */
-    for (auto& q : qcr) {
-      q = 0;
-    }
-    const auto ql = [&] {
-      if constexpr (QUAD) {
-        return QD::make_lanes(wave, lane, __builtin_amdgcn_readfirstlane(nof_layers));
-      } else {
-        return 0;
-      }
-    }();
-    /* the iteration loop; with a partial form (few-layer codeblocks: dec::iteration_partial) in two copies, the
-     * branch between them taken once per codeblock, outside the loop */
-    CB_STAMP(2);
-    auto run_iterations = [&](auto partial) __attribute__((always_inline)) {
-    for (int it = 0; it < d.max_iterations; ++it) {
-      if constexpr (QUAD) {
-        QD::iteration(qcr, qtab, ql);
-      } else if constexpr (SPEC) {
-        if constexpr (decltype(partial)::value) {
-          SD::iteration_partial(cr, sl);
-        } else {
-          SD::iteration(cr, sl, pf);
-        }
-      }
-      for (int g = 0; g < (SPEC ? 0 : n_steps); ++g) {
-#ifdef LDPC_HIP_DIAG
-        if (blockIdx.x == 0 && lane == 0 && it == d.max_iterations - 1) {
-          g_diag2[(g * 16 + wave) * 2] = __builtin_amdgcn_s_memtime();
-        }
-#endif
-        uint64_t ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        PHASE(7);
-        const step_task cur = nxt;
-        nxt                 = tk[(g + 1 < n_steps ? g + 1 : 0) * tw];
-        const uint32_t  h   = cur.w[0];
-        const int      row = static_cast<int>((h >> 8) & 0xffU);
-        if ((h & 64U) != 0U && row < nof_layers && !idle) {
-          const int deg     = static_cast<int>(h & 31U);
-          const int t0      = static_cast<int>(h >> 16);
-          int8_t*         c2v_row = s_c2v + cur.w[1];
-          const uint32_t* s_slot  = reinterpret_cast<const uint32_t*>(smem + cur.w[2]);
-          if ((h & 32U) != 0U) {
-            const int t = t0 + (lane & 31);
-            if (t < Z) {
-#ifndef LDPC_HIP_DIAG_SKIP
-              row_dispatch<2, SF08>(deg, t, half, s_slot + (half ? (deg + 1) / 2 : 0), s_soft, c2v_row, sf, Z,
-                                   trash, ph);
-#endif
-            }
-          } else {
-            const int t = t0 + lane;
-            if (t < Z) {
-#ifndef LDPC_HIP_DIAG_SKIP
-              row_dispatch<1, SF08>(deg, t, 0, s_slot, s_soft, c2v_row, sf, Z, trash, ph);
-#endif
-            }
-          }
-        }
-#ifdef LDPC_HIP_DIAG_PHASE
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        PHASE(5);
-        __syncthreads();
-        PHASE(6);
-        if (blockIdx.x == 0 && lane == 0 && it == d.max_iterations - 1) {
-          for (int q = 0; q < 8; ++q) {
-            g_diag2[(g * 16 + wave) * 8 + q] = ph[q];
-          }
-        }
-#endif
-#ifdef LDPC_HIP_DIAG
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (blockIdx.x == 0 && lane == 0 && it == d.max_iterations - 1) {
-          g_diag2[(g * 16 + wave) * 2 + 1] = __builtin_amdgcn_s_memtime();
-        }
-#endif
-        __syncthreads();
-#ifdef LDPC_HIP_DIAG
-        if (blockIdx.x == 0 && tid == 0 && diag_n < 4000) {
-          g_diag[diag_n++] = __builtin_amdgcn_s_memtime();
-        }
-#endif
-      }
-      hb_current = false;
-      if (d.crc_mode == LDPC_HIP_CRC_MODE_EARLY_STOP) {
-        const bool ok =
-            block_hard_decision<SPEC ? SG::g.Z : 0>(s_soft, s_hb, KZ, &s_red[30], static_cast<uint32_t>(it) + 1U, Z,
-                                                    SPEC ? static_cast<int>(lay.soft_stride) : 0,
-                                                    static_cast<int>(lay.soft_read));
-        hb_current    = true;
-        if (ok && block_crc(s_hb, Lsig, d.crc_poly, s_crct,
-                            s_red, crc_tables + CRC_MCOL_OFFSET + d.crc_poly * CRC_MCOL_WORDS) == 0) {
-          has_value  = 1;
-          iterations = it + 1;
-          break;
-        }
-      }
-    }
-    };
-    if constexpr (SPEC && !QUAD && SD::HAS_PARTIAL) {
-      if (__builtin_expect(nof_layers <= SD::PARTIAL_LAYERS, 0)) {
-        run_iterations(std::true_type{});
-      } else {
-        run_iterations(std::false_type{});
-      }
-    } else {
-      run_iterations(std::false_type{});
-    }
-    CB_STAMP(3);
-    if (!hb_current) {
-      block_hard_decision<SPEC ? SG::g.Z : 0>(s_soft, s_hb, KZ, &s_red[30], 0xffffffffU, Z,
-                                              SPEC ? static_cast<int>(lay.soft_stride) : 0,
-                                              static_cast<int>(lay.soft_read));
-    }
-    if (d.crc_mode == LDPC_HIP_CRC_MODE_CHECK_AFTER) {
-      has_value = (block_crc(s_hb, Lsig, d.crc_poly, s_crct,
-                             s_red, crc_tables + CRC_MCOL_OFFSET + d.crc_poly * CRC_MCOL_WORDS) == 0);
-    }
-  }
-
-  CB_STAMP(4);
-  if (write_out) {
-    for (int b = tid; b < nb; b += nthr) {
-      out[b] = s_hb[b];
-    }
-  }
-  if (tid == 0 && res_base != nullptr) {
-    ldpc_hip_cb_result r;
-    r.crc_pass               = static_cast<uint8_t>(has_value);
-    r.nof_iterations         = static_cast<uint8_t>(iterations);
-    r.status                 = write_out ? LDPC_HIP_STATUS_OUTPUT_WRITTEN : 0;
-    res_base[d.result_index] = r;
-  }
-  CB_STAMP(5);
-#undef CB_STAMP
-#undef graph
-}
-
-/* threads per workgroup at most: the generic body 16 waves, a specialised one 12 (up to 168 VGPRs) */
-template <int SPEC_ID>
-constexpr int decode_max_threads()
-{
-  return SPEC_ID < 0 ? 1024 : 768;
-}
-
-template <bool SF08, int SPEC_ID>
-__global__ void __launch_bounds__(decode_max_threads<SPEC_ID>())
-    ldpc_decode_kernel(const dec_cb* __restrict__ cbs, dec_cb one, int graph_slot, const step_task* __restrict__ tasks,
-                       lds_layout lay, const int8_t* llr_base, uint8_t* __restrict__ out_base,
-                       ldpc_hip_cb_result* __restrict__ res_base, const uint32_t* __restrict__ crc_tables,
-                       const dematch_cb* dm_cbs, dematch_cb dm_one)
-{
-  /* cbs == nullptr: a one-CB launch whose descriptor came by value in the kernel arguments (no dependent load from
-   * the descriptor table before the first LLR load; the HAL's zero-copy tables are in host memory).
-   * llr_base is not __restrict__: with the fused dematcher (dm_cbs / dm_one) the workgroup first writes the soft
-   * buffer it then reads through llr_base, through the dematch descriptor's pointer. */
-  decode_cb<SF08, SPEC_ID>(cbs != nullptr ? cbs[blockIdx.x] : one, graph_slot, tasks, lay, llr_base, out_base, res_base,
-                           crc_tables, dm_cbs, dm_one);
-}
-
-/* ---- device work queue: the persistent loop of a unit's grid (ldpc_hip_dwq.cpp) ------------------------------------
- * Wave 0 of a workgroup polls the ring slot of the next ticket, `next` (its view of the device claim counter): one
- * round trip reads the slot's 48 words (lanes 0-47) and the host's stop word (lane 48) from pinned memory. A slot whose
- * three sequence words equal next + 1 holds a published item; lane 0 claims it with a device-scope CAS of the claim
- * counter (next -> next + 1), and the item, already in registers, goes to LDS. A failed CAS returns the counter's
- * value, which becomes `next` (another workgroup claimed it). Only published items are ever claimed, so a workgroup
- * that leaves never strands one. Idle workgroups poll in turns (workgroup b in the 0.25 us slots where
- * (t / slot) mod grid = b: one slot read per 0.25 us for the grid); a workgroup that has just finished an item polls
- * twice at once, and one that lost a claim polls again at once, so back-to-back work does not wait for a turn
- * (polling freely for 20 us after seeing work, measured in round 4, cost more PCIe and host-cache traffic than it
- * saved, profiles/r04/route_ab_eager_v1.json). The body runs (fused
- * dematch + specialised decode, or a dematch alone), every wave drains its stores, and after a barrier lane 0 makes the
- * workgroup's writes visible system-wide (release fence: the HARQ soft bits in HBM for the next transmission's
- * workgroup on any XCD, the results in pinned host memory) and stores the done flag. Every wave leaves the loop
- * together: after idle_ticks without work, after life_ticks in all, or on stop; the host relaunches a grid when it
- * finds work unclaimed and the grid gone (ldpc_hip_dwq.cpp). Every spin is bounded. */
-constexpr uint32_t DWQ_NONE = 0xffffffffU;
-template <class BODY>
-__device__ __forceinline__ void dwq_loop(const dwq_args& a, BODY&& body)
-{
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  /* control words: [0] claimed ticket, [1] stop, [2] ticks from t0 to the claim, [3] / [4] t0; the item from [8] */
-  uint32_t* s_ctl  = reinterpret_cast<uint32_t*>(smem + a.ctl_lds);
-  uint32_t* s_item = s_ctl + 8;
-  const int tid    = threadIdx.x;
-  const int lane   = tid & 63;
-  uint64_t  t0     = __builtin_amdgcn_s_memrealtime();
-  uint64_t  last   = t0;
-  uint32_t  next   = 0; /* wave 0: the next ticket to poll */
-  uint32_t  quick  = 0; /* wave 0: polls left outside the turns (the first ones after an item) */
-  if (tid == 0) {
-    s_ctl[3] = static_cast<uint32_t>(t0);
-    s_ctl[4] = static_cast<uint32_t>(t0 >> 32);
-  }
-  if (tid < 64) {
-    next = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(
-        __hip_atomic_load(a.dev_ctl + DWQ_D_CLAIMED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))));
-  }
-#ifdef LDPC_HIP_DIAG_DWQ /* diagnostic build: lane 0's 100 MHz stamps of each item, into dead words of its slot */
-  uint64_t t_claim = 0;
-#endif
-  while (true) {
-    if (tid < 64) {
-      uint32_t       claim = DWQ_NONE, stop = 0;
-      const uint64_t tin   = __builtin_amdgcn_s_memrealtime();
-      while (claim == DWQ_NONE && stop == 0U) {
-        const uint64_t now = __builtin_amdgcn_s_memrealtime();
-        if (now - tin > 1000U) { /* 10 us: back to the idle / lifetime checks */
-          break;
-        }
-        if (quick == 0U) {
-          const uint32_t slot = static_cast<uint32_t>(now / a.slot_ticks);
-          const uint32_t ahead = (blockIdx.x + gridDim.x - slot % gridDim.x) % gridDim.x; /* slots to this turn */
-          if (ahead != 0U) {
-            if ((a.poll_flags & DWQ_POLL_LONG_SLEEP) != 0U && ahead * a.slot_ticks > 100U) {
-              __builtin_amdgcn_s_sleep(32); /* ~2,048 cycles, ~0.85 us at 2.4 GHz */
-            } else {
-              __builtin_amdgcn_s_sleep(2);
-            }
-            continue;
-          }
-        }
-        quick = quick != 0U ? quick - 1U : 0U;
-        const uint32_t* sw = a.ring + (next & a.ring_mask) * DWQ_WIRE_WORDS;
-        uint32_t        w  = 0;
-        if (lane < static_cast<int>(DWQ_WIRE_WORDS)) {
-          w = __hip_atomic_load(sw + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        } else if (lane == static_cast<int>(DWQ_WIRE_WORDS)) {
-          w = __hip_atomic_load(a.host_ctl + DWQ_H_STOP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        auto lane_word = [&](int l) {
-          return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(w), l));
-        };
-        stop                = lane_word(DWQ_WIRE_WORDS);
-        if (stop != 0U || (a.poll_flags & DWQ_POLL_TEST_NO_CLAIM) != 0U) {
-          /* a stopped grid claims nothing more (a timed-out wait on the host stops it and then takes its exit as the
-           * point after which no item of the queue can touch the caller's buffers, dwq_wait) */
-          continue;
-        }
-        const uint32_t want = next + 1U;
-        /* the checksum of payload words 0-43 (lane l carries payload word l - l / 16) against word 44 (lane 46) */
-        const int      pw   = lane - (lane >> 4);
-        const uint32_t mx   = (lane < static_cast<int>(DWQ_WIRE_WORDS) && (lane & 15) != 15 && pw < 44)
-                                  ? dwq_mix(w, static_cast<uint32_t>(pw)) : 0U;
-        const uint32_t sum  = wave_xor(mx);
-        if (lane_word(15) == want && lane_word(31) == want && lane_word(47) == want && sum == lane_word(46)) {
-          uint32_t exp = next;
-          uint32_t ok  = 0;
-          if (lane == 0) {
-            /* relaxed: the item is already in registers (validated by its sequence words), the previous item's
-             * writes were released with its done flag, and the acquire for the HARQ memory follows the claim; an
-             * acq_rel CAS wrote back and invalidated the L2 around it on every claim */
-            ok = __hip_atomic_compare_exchange_strong(a.dev_ctl + DWQ_D_CLAIMED, &exp, next + 1U, __ATOMIC_RELAXED,
-                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                     ? 1U
-                     : 0U;
-          }
-          ok  = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(ok)));
-          exp = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(exp)));
-          if (ok != 0U) {
-            claim = next;
-            next  = next + 1U;
-            if (lane < static_cast<int>(DWQ_WIRE_WORDS) && (lane & 15) != 15) {
-              s_item[lane - (lane >> 4)] = w;
-            } else if (lane >= 61) {
-              s_item[DWQ_WIRE_PAYLOAD + (lane - 61)] = 0; /* pad[1..3] */
-            }
-          } else {
-            next  = exp; /* another workgroup claimed it: poll the counter's next ticket at once */
-            quick = quick != 0U ? quick : 1U;
-          }
-          continue;
-        }
-        __builtin_amdgcn_s_sleep(2);
-      }
-      if (claim != DWQ_NONE) {
-        /* the HARQ soft bits an earlier item left in HBM, possibly from another XCD's L2, and the host's new inputs
-         * in pinned staging this CU's vector cache may hold from an earlier item (a timing variant without this
-         * acquire decoded stale LLRs) */
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      }
-      const uint64_t now = __builtin_amdgcn_s_memrealtime();
-#ifdef LDPC_HIP_DIAG_DWQ
-      t_claim = now;
-#endif
-      if (lane == 0) {
-        s_ctl[0] = claim;
-        s_ctl[1] = stop;
-        s_ctl[2] = static_cast<uint32_t>(now - t0);
-      }
-    }
-    __syncthreads();
-    const uint32_t claim   = s_ctl[0];
-    const uint32_t stop    = s_ctl[1];
-    const uint64_t elapsed = s_ctl[2];
-    if (claim == DWQ_NONE) {
-      __syncthreads(); /* every wave has read the control words before wave 0 writes them again */
-      if (stop != 0U || elapsed - (last - t0) > a.idle_ticks || elapsed > a.life_ticks) {
-        break;
-      }
-      continue;
-    }
-    /* The item's words go to scalar registers (the launched kernel's descriptor comes from the kernel arguments into
-     * SGPRs as well): a vector-register copy lived across the body and made the BG1 bodies spill. Nothing of the loop
-     * lives in registers across the body: its state is rebuilt from the control words after it. */
-    uint32_t words[DWQ_ITEM_WORDS];
-    for (uint32_t k = 0; k != DWQ_ITEM_WORDS; ++k) {
-      words[k] = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(s_item[k])));
-    }
-    /* memcpy, not stores through a uint32_t* into the struct: its 64-, 16- and 8-bit fields read back after such
-     * stores are not ordered after them under type-based alias analysis (a loop-carried `it` then handed the body some
-     * fields of the workgroup's previous item: wrong decodes of successive calls with different lengths) */
-    dwq_item it;
-    __builtin_memcpy(&it, words, sizeof(it));
-#ifdef LDPC_HIP_DIAG_DWQ
-    const uint64_t t_item = __builtin_amdgcn_s_memrealtime();
-#endif
-    if (it.spec != DWQ_SPEC_NOOP) {
-      body(it);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const uint32_t done_claim = s_ctl[0];
-    t0    = (static_cast<uint64_t>(s_ctl[4]) << 32) | s_ctl[3];
-    last  = t0 + s_ctl[2];
-    next  = done_claim + 1U;
-    quick = 2U; /* a workgroup done with an item looks at the next ticket at once (back-to-back work), twice */
-    if (tid == 0) {
-#ifdef LDPC_HIP_DIAG_DWQ
-      uint32_t* pw = const_cast<uint32_t*>(a.ring + (claim & a.ring_mask) * DWQ_WIRE_WORDS);
-      pw[44]       = static_cast<uint32_t>(t_claim);
-      pw[45]       = static_cast<uint32_t>(t_item - t_claim);
-      pw[46]       = static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime() - t_claim);
-      pw[14]       = blockIdx.x;
-#endif
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-      __hip_atomic_store(a.done + (done_claim & a.ring_mask), done_claim + 1U, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-  /* the grid's last workgroup to leave tells the host (ldpc_hip_dwq.cpp ensure_running: no runtime query per submit) */
-  if (tid == 0) {
-    const uint32_t n = __hip_atomic_fetch_add(a.dev_ctl + DWQ_D_EXITS, 1U, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (n + 1U == a.exit_target) {
-      __hip_atomic_store(a.host_exit, a.exit_target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-}
-
-/* The work-queue kernels: one per specialised graph (its fused dematch + decode body only) and one for dematch-only
- * items, so each has the register allocation of its own body. Round 4 first had one kernel per translation unit that
- * dispatched on it.spec among the unit's 4-10 bodies: the union spilled 24-137 VGPRs to scratch and 189-518 SGPRs
- * (the launched kernels of the same bodies spill none), and its bodies ran up to 1.5x slower than launched ones. */
-template <int SPEC_ID>
-__global__ void __launch_bounds__(decode_max_threads<SPEC_ID>()) ldpc_dwq_decode_kernel(dwq_args a)
-{
-  dwq_loop(a, [&](const dwq_item& it) __attribute__((always_inline)) {
-    decode_cb<true, SPEC_ID>(it.cb, 0, nullptr, it.lay, it.llr_base, it.out_base, it.res_base, it.crc_tables, nullptr,
-                             dm_plain(it.dm));
-  });
-}
-
-/* Diagnostic build (LDPC_HIP_DIAG): each specialised-kernel unit has its own static g_diag2 (the stamps of its
- * kernels), read by ldpc_hip_diag2_read_<unit> (tools/diag_timeline.py); nothing in other builds. */
-#if defined(LDPC_HIP_DIAG)
-#define LDPC_DIAG_UNIT_READER(u)                                                                                       \
-  extern "C" int ldpc_hip_diag2_read_##u(uint64_t* out, uint32_t n)                                                  \
-  {                                                                                                                    \
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_diag2), n * sizeof(uint64_t)) == hipSuccess ? 0 : -2;               \
-  }
-#else
-#define LDPC_DIAG_UNIT_READER(u)
-#endif
-
-/* dwq_kernel_<unit>(id): the work-queue kernel of specialised graph id of the unit's list, nullptr for other ids */
-#define LDPC_DWQ_KERNEL_CASE(id, bg, z, ils)                                                                           \
-  case id: return reinterpret_cast<const void*>(&ldpc_dwq_decode_kernel<id>);
-#define LDPC_DWQ_KERNELS(NAME, LIST)                                                                                   \
-  const void* NAME(int id)                                                                                             \
-  {                                                                                                                    \
-    switch (id) {                                                                                                      \
-      LIST(LDPC_DWQ_KERNEL_CASE)                                                                                       \
-    default: return nullptr;                                                                                           \
-    }                                                                                                                  \
-  }
-
-/* The split-row address table of specialised graph SPEC_ID into dst (dec::write_split_table), or for a one-wave graph
- * its lane-split decoder's address table (qdec::write_table): one workgroup of the decoder's width, launched once per
- * context (ldpc_hip_kernels.hip write_split_tables). */
-template <int SPEC_ID>
-__global__ void __launch_bounds__(768) ldpc_split_table_kernel(uint32_t* __restrict__ dst)
-{
-  using SG = spec::spec_graph<SPEC_ID>;
-  using SD = sp::dec<SG::g>;
-  if constexpr (spec::is_quad(SG::g)) { /* the lane-split decoder's address table (sp::qdec) */
-    sp::qdec<SG::g, SG::q>::write_table(dst, static_cast<int>(threadIdx.x >> 6), static_cast<int>(threadIdx.x & 63),
-                                        std::make_integer_sequence<int, SG::q.n_steps>{});
-  } else if constexpr (SD::LDS_PAIRS > 0) {
-    SD::write_split_table(dst, static_cast<int>(threadIdx.x >> 6), static_cast<int>(threadIdx.x & 63));
-  }
-}
-
-
 } // namespace ldpc_hip

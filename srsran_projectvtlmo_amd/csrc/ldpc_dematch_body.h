@@ -1,10 +1,13 @@
 /*
  * Rate dematching (ldpc_rate_dematcher_impl.cpp:46-213) and the soft demodulation it can fuse
  * (demodulation_mapper_impl.cpp:78-106), as device functions: ldpc_rate_dematch_kernel and ldpc_demodulate_kernel
- * (ldpc_hip_kernels.hip) run them standalone, the decode kernels (ldpc_decode_body.h) as a fused first phase.
- * Included by ldpc_decode_body.h after its LLR helpers (llr_isinf, LLR_MAX, LLR_INF), in the same namespaces.
+ * (ldpc_hip_kernels.hip) run them standalone, the decode kernels (ldpc_decode_cb.h) as a fused first phase.
+ * Its phase stamps (DM_STAMP) are a diagnostic build's (ldpc_diag.h).
  */
 #pragma once
+
+#include "ldpc_device_util.h"
+#include "ldpc_diag.h"
 
 namespace ldpc_hip {
 namespace {
@@ -239,27 +242,12 @@ __device__ __forceinline__ dematch_cb dm_plain(const dematch_cb_base& b)
 }
 
 /* The dematcher's work for codeblock d: ldpc_rate_dematch_kernel's body, and the decode kernels' fused first phase
- * (ldpc_decode_body.h decode_cb, before the decoder prologue). s_in: DM_STAGE bytes of LDS staging; s_dtab: an LDS copy
+ * (ldpc_decode_cb.h decode_cb, before the decoder prologue). s_in: DM_STAGE bytes of LDS staging; s_dtab: an LDS copy
  * of the demodulation tables (soft-demodulating form only). Uses the whole workgroup (any width); leaves the LDS and
  * the soft buffer written but issues no final barrier. */
 __device__ __forceinline__ void dematch_body(const dematch_cb& d, const demod_tables& tab, int8_t* s_in,
                                              demod_tables& s_dtab)
 {
-#if defined(LDPC_HIP_DIAG_CB_DM) /* diagnostic build: the decoder's per-workgroup stamp slots 1-3 (decode_cb then skips
-                                    * its own stamps 1-3), at the context's table buffer (tab sits at DTAB_OFFSET) */
-#define DM_STAMP(k)                                                                                                    \
-  if (threadIdx.x == 0 && blockIdx.x < 1024) {                                                                         \
-    reinterpret_cast<uint64_t*>(const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(&tab) - DTAB_OFFSET) +       \
-                                DIAG_CB_OFFSET)[blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime();             \
-  }
-#elif defined(LDPC_HIP_DIAG_DM) /* diagnostic build: device-wide 100 MHz stamps per workgroup (g_diag2[block * 8 + k]) */
-#define DM_STAMP(k)                                                                                                    \
-  if (threadIdx.x == 0 && blockIdx.x < 1024) {                                                                         \
-    g_diag2[blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime();                                                  \
-  }
-#else
-#define DM_STAMP(k)
-#endif
   const int        tid = threadIdx.x;
   const int        nth = blockDim.x;
 
@@ -484,7 +472,6 @@ __device__ __forceinline__ void dematch_body(const dematch_cb& d, const demod_ta
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   DM_STAMP(3);
 #endif
-#undef DM_STAMP
 }
 
 } // namespace

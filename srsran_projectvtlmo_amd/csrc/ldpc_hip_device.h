@@ -89,7 +89,7 @@ struct step_task {
  * groups[g]  = first row | rows << 8 | P << 16      consecutive rows that share no variable node; P = 2 splits
  *              each check node's edges over lanes l and l ^ 32
  * c2v_off[m] = byte offset of row m's check-to-variable messages in the LDS c2v area: int8 c2v[e][t] for the
- *              row's edges e, stride Z (ldpc_hip_kernels.hip "Check-to-variable storage").               */
+ *              row's edges e, stride Z (ldpc_decode_row.h "Check-to-variable storage").               */
 struct graph_desc {
   uint8_t  bg;
   uint8_t  maxdeg;

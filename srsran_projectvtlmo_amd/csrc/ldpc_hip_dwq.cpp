@@ -4,7 +4,7 @@
  * count, and done flags in pinned memory the kernel writes. Per device: a pool of CU-masked streams (one hardware queue
  * each) that bounds how many grids are resident at once (the residency budget).
  *
- * Protocol (device side: dwq_loop, ldpc_decode_body.h):
+ * Protocol (device side: dwq_loop, ldpc_dwq_loop.h):
  *   submit  under the queue mutex: wait for the ring slot's previous item to be done, write the item into the slot
  *           (three lines, each line's sequence word = ticket + 1 written after its payload; word 44 a checksum of the
  *           item's words 0-43), make sure a grid is running (launching one on a free pool stream);
@@ -39,7 +39,7 @@ namespace {
 /* the persistent kernel of a queue key: 0 dematch-only items, 1 + id the specialised graph id (found in its unit) */
 const void* key_kernel(int key)
 {
-#define LDPC_DWQ_UNIT_PTR(u) dwq_kernel_##u,
+#define LDPC_DWQ_UNIT_PTR(u, x) dwq_kernel_##u,
   static const void* (*const k[])(int) = {LDPC_KERNEL_UNITS(LDPC_DWQ_UNIT_PTR)};
 #undef LDPC_DWQ_UNIT_PTR
   if (key == 0) {

@@ -1,5 +1,6 @@
 /*
- * The host launchers of the kernel units, declared once: ldpc_hip_kernels.hip and ldpc_spec_kernels_*.hip define them
+ * The host launchers of the kernel units, declared once: ldpc_hip_kernels.hip (with ldpc_uplink_kernels.h),
+ * ldpc_downlink_kernels.hip and ldpc_spec_unit.hip define them
  * and the host runtime calls them, all through this header, so a signature or default argument cannot drift.
  * (spec_waves, quad_table_offset and the other schedule queries of ldpc_graph.cpp are in ldpc_graph.h.)
  */
@@ -12,8 +13,10 @@
 
 namespace ldpc_hip {
 
-/* ---- ldpc_hip_kernels.hip ---- */
+/* ---- ldpc_hip_kernels.hip and the uplink family it includes; ldpc_downlink_kernels.hip: upload_encoder_graphs (called
+ * by upload_graphs), launch_encode, launch_rate_match, launch_pdsch_encode, dwq_kernel_encode, dwq_kernel_copy ---- */
 hipError_t upload_graphs(const graph_desc* graphs, int n);
+hipError_t upload_encoder_graphs(const graph_desc* graphs, int n);
 hipError_t configure_kernels(uint32_t max_lds);
 hipError_t write_split_tables(uint32_t* d_tables, const int* spec_ids, hipStream_t stream);
 /* host_one / host_dm_one: a one-CB launch's descriptors by value; d_dm: the fused dematcher's, dm_lds its LDS budget */
@@ -46,20 +49,13 @@ const void* dwq_kernel_dematch();
 const void* dwq_kernel_encode();
 const void* dwq_kernel_copy();
 
-/* ---- every kernel unit: the host launch stubs of its specialised kernels and split-row table writers, and the
- * work-queue kernel of specialised graph id (nullptr when the unit does not hold it) ---- */
-/* the kernel units (core: ldpc_hip_kernels.hip; a..p: ldpc_spec_kernels_<u>.hip, spec_unit() 1..16) and the
- * specialised graphs of units a..p, in unit order */
-#define LDPC_KERNEL_UNITS(X) X(core) X(a) X(b) X(c) X(d) X(e) X(f) X(g) X(h) X(i) X(j) X(k) X(l) X(m) X(n) X(o) X(p)
-#define LDPC_SPEC_GRAPHS_UNITS(X)                                                                                      \
-  LDPC_SPEC_GRAPHS_MID_A(X) LDPC_SPEC_GRAPHS_MID_B(X) LDPC_SPEC_GRAPHS_MID_C(X) LDPC_SPEC_GRAPHS_MID_D(X)              \
-  LDPC_SPEC_GRAPHS_MID_E(X) LDPC_SPEC_GRAPHS_MID_F(X) LDPC_SPEC_GRAPHS_MID_G(X) LDPC_SPEC_GRAPHS_MID_H(X)              \
-  LDPC_SPEC_GRAPHS_SMALL_I(X) LDPC_SPEC_GRAPHS_SMALL_J(X) LDPC_SPEC_GRAPHS_SMALL_K(X) LDPC_SPEC_GRAPHS_SMALL_L(X)      \
-  LDPC_SPEC_GRAPHS_SMALL_M(X) LDPC_SPEC_GRAPHS_SMALL_N(X) LDPC_SPEC_GRAPHS_SMALL_O(X) LDPC_SPEC_GRAPHS_SMALL_P(X)
+/* ---- every kernel unit (ldpc_spec.h LDPC_KERNEL_UNITS: core is ldpc_hip_kernels.hip, a..p are ldpc_spec_unit.hip
+ * compiled per letter, spec_unit() 1..16): the host launch stubs of its specialised kernels and split-row table
+ * writers, and the work-queue kernel of specialised graph id (nullptr when the unit does not hold it) ---- */
 #define LDPC_SPEC_KERNEL_DECL(id, bg, z, ils) const void* spec_kernel_##id(); const void* spec_split_kernel_##id();
 LDPC_SPEC_GRAPHS_UNITS(LDPC_SPEC_KERNEL_DECL)
 #undef LDPC_SPEC_KERNEL_DECL
-#define LDPC_DWQ_UNIT_DECL(u) const void* dwq_kernel_##u(int id);
+#define LDPC_DWQ_UNIT_DECL(u, x) const void* dwq_kernel_##u(int id);
 LDPC_KERNEL_UNITS(LDPC_DWQ_UNIT_DECL)
 #undef LDPC_DWQ_UNIT_DECL
 

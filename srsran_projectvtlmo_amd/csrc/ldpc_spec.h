@@ -451,41 +451,63 @@ constexpr qgraph make_quad(const sgraph& g)
 }
 
 /* The (BG, Z) pairs with a specialised kernel, X(id, bg, Z, ils); ils is the lifting set of Z (TS 38.212 Table
- * 5.3.2-1). The kernel is instantiated per id.
- *  - core (ids 0-9, ldpc_hip_kernels.hip, also bodies of the mixed kernel): BG1 Z = 384 (the BASELINE metric's graph)
- *    and the other large lifting sizes the codeblocks of large transport blocks use, BG1 and BG2 with Z in {384, 352,
- *    320, 288, 256};
- *  - mid (ids 10-41, ldpc_spec_kernels_{a..h}.hip, own launches only): BG1 and BG2 with Z in {240, 224, 208, 192,
- *    176, 160, 144, 128} (C3's BG2 Z = 208 among them) and {120, 112, 104, 96, 88, 80, 72, 64};
- *  - small (ids 42-101, ldpc_spec_kernels_{i..p}.hip, own launches only): every lifting size below 64 (a row is less
- *    than one wave: lanes t >= Z idle, two waves per codeblock).
+ * 5.3.2-1). The kernel is instantiated per id; ids run 0, 1, 2, ... in list order.
+ *  - core (ids 0-9, ldpc_hip_kernels.hip, also bodies of the mixed kernel): BG1 Z = 384 (the BASELINE metric's
+ *    graph) and the other large lifting sizes the codeblocks of large transport blocks use, BG1 and BG2 with Z in
+ *    {384, 352, 320, 288, 256};
+ *  - mid (ids 10-41, units a..h, own launches only): BG1 and BG2 with Z in {240, 224, 208, 192, 176, 160, 144, 128}
+ *    (C3's BG2 Z = 208 among them) and {120, 112, 104, 96, 88, 80, 72, 64};
+ *  - small (ids 42-101, units i..p, own launches only): every lifting size below 64 (a row is less than one wave:
+ *    lanes t >= Z idle, two waves per codeblock).
  * In a mixed launch the mid and small graphs run the generic body. */
 #define LDPC_SPEC_GRAPHS_CORE(X)                                                                                       \
   X(0, 1, 384, 1) X(1, 1, 352, 5) X(2, 1, 320, 2) X(3, 1, 288, 4) X(4, 1, 256, 0)                                      \
   X(5, 2, 384, 1) X(6, 2, 352, 5) X(7, 2, 320, 2) X(8, 2, 288, 4) X(9, 2, 256, 0)
-#define LDPC_SPEC_GRAPHS_MID_A(X) X(10, 1, 240, 7) X(11, 1, 224, 3) X(12, 1, 208, 6) X(13, 1, 192, 1)
-#define LDPC_SPEC_GRAPHS_MID_B(X) X(14, 1, 176, 5) X(15, 1, 160, 2) X(16, 1, 144, 4) X(17, 1, 128, 0)
-#define LDPC_SPEC_GRAPHS_MID_C(X) X(18, 2, 240, 7) X(19, 2, 224, 3) X(20, 2, 208, 6) X(21, 2, 192, 1)
-#define LDPC_SPEC_GRAPHS_MID_D(X) X(22, 2, 176, 5) X(23, 2, 160, 2) X(24, 2, 144, 4) X(25, 2, 128, 0)
-#define LDPC_SPEC_GRAPHS_MID_E(X) X(26, 1, 120, 7) X(27, 1, 112, 3) X(28, 1, 104, 6) X(29, 1, 96, 1)
-#define LDPC_SPEC_GRAPHS_MID_F(X) X(30, 1, 88, 5) X(31, 1, 80, 2) X(32, 1, 72, 4) X(33, 1, 64, 0)
-#define LDPC_SPEC_GRAPHS_MID_G(X) X(34, 2, 120, 7) X(35, 2, 112, 3) X(36, 2, 104, 6) X(37, 2, 96, 1)
-#define LDPC_SPEC_GRAPHS_MID_H(X) X(38, 2, 88, 5) X(39, 2, 80, 2) X(40, 2, 72, 4) X(41, 2, 64, 0)
-#define LDPC_SPEC_GRAPHS_SMALL_I(X) X(42, 1, 60, 7) X(43, 1, 56, 3) X(44, 1, 52, 6) X(45, 1, 48, 1) X(46, 1, 44, 5) X(47, 1, 40, 2) X(48, 1, 36, 4) X(49, 1, 32, 0)
-#define LDPC_SPEC_GRAPHS_SMALL_J(X) X(50, 1, 30, 7) X(51, 1, 28, 3) X(52, 1, 26, 6) X(53, 1, 24, 1) X(54, 1, 22, 5) X(55, 1, 20, 2) X(56, 1, 18, 4) X(57, 1, 16, 0)
-#define LDPC_SPEC_GRAPHS_SMALL_K(X) X(58, 1, 15, 7) X(59, 1, 14, 3) X(60, 1, 13, 6) X(61, 1, 12, 1) X(62, 1, 11, 5) X(63, 1, 10, 2) X(64, 1, 9, 4) X(65, 1, 8, 0)
-#define LDPC_SPEC_GRAPHS_SMALL_L(X) X(66, 1, 7, 3) X(67, 1, 6, 1) X(68, 1, 5, 2) X(69, 1, 4, 0) X(70, 1, 3, 1) X(71, 1, 2, 0) X(72, 2, 60, 7) X(73, 2, 56, 3)
-#define LDPC_SPEC_GRAPHS_SMALL_M(X) X(74, 2, 52, 6) X(75, 2, 48, 1) X(76, 2, 44, 5) X(77, 2, 40, 2) X(78, 2, 36, 4) X(79, 2, 32, 0) X(80, 2, 30, 7) X(81, 2, 28, 3)
-#define LDPC_SPEC_GRAPHS_SMALL_N(X) X(82, 2, 26, 6) X(83, 2, 24, 1) X(84, 2, 22, 5) X(85, 2, 20, 2) X(86, 2, 18, 4) X(87, 2, 16, 0) X(88, 2, 15, 7) X(89, 2, 14, 3)
-#define LDPC_SPEC_GRAPHS_SMALL_O(X) X(90, 2, 13, 6) X(91, 2, 12, 1) X(92, 2, 11, 5) X(93, 2, 10, 2) X(94, 2, 9, 4) X(95, 2, 8, 0) X(96, 2, 7, 3) X(97, 2, 6, 1)
-#define LDPC_SPEC_GRAPHS_SMALL_P(X) X(98, 2, 5, 2) X(99, 2, 4, 0) X(100, 2, 3, 1) X(101, 2, 2, 0)
-#define LDPC_SPEC_GRAPHS(X)                                                                                            \
-  LDPC_SPEC_GRAPHS_CORE(X)                                                                                             \
-  LDPC_SPEC_GRAPHS_MID_A(X) LDPC_SPEC_GRAPHS_MID_B(X) LDPC_SPEC_GRAPHS_MID_C(X) LDPC_SPEC_GRAPHS_MID_D(X)              \
-  LDPC_SPEC_GRAPHS_MID_E(X) LDPC_SPEC_GRAPHS_MID_F(X) LDPC_SPEC_GRAPHS_MID_G(X) LDPC_SPEC_GRAPHS_MID_H(X)              \
-  LDPC_SPEC_GRAPHS_SMALL_I(X) LDPC_SPEC_GRAPHS_SMALL_J(X) LDPC_SPEC_GRAPHS_SMALL_K(X) LDPC_SPEC_GRAPHS_SMALL_L(X)      \
-  LDPC_SPEC_GRAPHS_SMALL_M(X) LDPC_SPEC_GRAPHS_SMALL_N(X) LDPC_SPEC_GRAPHS_SMALL_O(X) LDPC_SPEC_GRAPHS_SMALL_P(X)
-constexpr int NOF_CORE_SPECS = 10; /* ids [0, 10): bodies of the mixed kernel */
+
+/* The unit table: the graphs outside the core are dealt over kernel units that compile in parallel, each
+ * ldpc_spec_unit.hip compiled with -DLDPC_SPEC_UNIT=<letter> (the Makefile's SPEC_UNITS is the only other list of the
+ * letters). LDPC_SPEC_GRAPHS_UNIT_<u>(X): unit u's graphs; LDPC_SPEC_UNITS(U, X): U(u, X) per unit, in id order.
+ * Everything else that depends on the units is derived below and in ldpc_hip_launch.h (the kernel declarations) and
+ * ldpc_graph.cpp (spec_unit). */
+#define LDPC_SPEC_GRAPHS_UNIT_a(X) X(10, 1, 240, 7) X(11, 1, 224, 3) X(12, 1, 208, 6) X(13, 1, 192, 1)
+#define LDPC_SPEC_GRAPHS_UNIT_b(X) X(14, 1, 176, 5) X(15, 1, 160, 2) X(16, 1, 144, 4) X(17, 1, 128, 0)
+#define LDPC_SPEC_GRAPHS_UNIT_c(X) X(18, 2, 240, 7) X(19, 2, 224, 3) X(20, 2, 208, 6) X(21, 2, 192, 1)
+#define LDPC_SPEC_GRAPHS_UNIT_d(X) X(22, 2, 176, 5) X(23, 2, 160, 2) X(24, 2, 144, 4) X(25, 2, 128, 0)
+#define LDPC_SPEC_GRAPHS_UNIT_e(X) X(26, 1, 120, 7) X(27, 1, 112, 3) X(28, 1, 104, 6) X(29, 1, 96, 1)
+#define LDPC_SPEC_GRAPHS_UNIT_f(X) X(30, 1, 88, 5) X(31, 1, 80, 2) X(32, 1, 72, 4) X(33, 1, 64, 0)
+#define LDPC_SPEC_GRAPHS_UNIT_g(X) X(34, 2, 120, 7) X(35, 2, 112, 3) X(36, 2, 104, 6) X(37, 2, 96, 1)
+#define LDPC_SPEC_GRAPHS_UNIT_h(X) X(38, 2, 88, 5) X(39, 2, 80, 2) X(40, 2, 72, 4) X(41, 2, 64, 0)
+#define LDPC_SPEC_GRAPHS_UNIT_i(X) X(42, 1, 60, 7) X(43, 1, 56, 3) X(44, 1, 52, 6) X(45, 1, 48, 1) X(46, 1, 44, 5) X(47, 1, 40, 2) X(48, 1, 36, 4) X(49, 1, 32, 0)
+#define LDPC_SPEC_GRAPHS_UNIT_j(X) X(50, 1, 30, 7) X(51, 1, 28, 3) X(52, 1, 26, 6) X(53, 1, 24, 1) X(54, 1, 22, 5) X(55, 1, 20, 2) X(56, 1, 18, 4) X(57, 1, 16, 0)
+#define LDPC_SPEC_GRAPHS_UNIT_k(X) X(58, 1, 15, 7) X(59, 1, 14, 3) X(60, 1, 13, 6) X(61, 1, 12, 1) X(62, 1, 11, 5) X(63, 1, 10, 2) X(64, 1, 9, 4) X(65, 1, 8, 0)
+#define LDPC_SPEC_GRAPHS_UNIT_l(X) X(66, 1, 7, 3) X(67, 1, 6, 1) X(68, 1, 5, 2) X(69, 1, 4, 0) X(70, 1, 3, 1) X(71, 1, 2, 0) X(72, 2, 60, 7) X(73, 2, 56, 3)
+#define LDPC_SPEC_GRAPHS_UNIT_m(X) X(74, 2, 52, 6) X(75, 2, 48, 1) X(76, 2, 44, 5) X(77, 2, 40, 2) X(78, 2, 36, 4) X(79, 2, 32, 0) X(80, 2, 30, 7) X(81, 2, 28, 3)
+#define LDPC_SPEC_GRAPHS_UNIT_n(X) X(82, 2, 26, 6) X(83, 2, 24, 1) X(84, 2, 22, 5) X(85, 2, 20, 2) X(86, 2, 18, 4) X(87, 2, 16, 0) X(88, 2, 15, 7) X(89, 2, 14, 3)
+#define LDPC_SPEC_GRAPHS_UNIT_o(X) X(90, 2, 13, 6) X(91, 2, 12, 1) X(92, 2, 11, 5) X(93, 2, 10, 2) X(94, 2, 9, 4) X(95, 2, 8, 0) X(96, 2, 7, 3) X(97, 2, 6, 1)
+#define LDPC_SPEC_GRAPHS_UNIT_p(X) X(98, 2, 5, 2) X(99, 2, 4, 0) X(100, 2, 3, 1) X(101, 2, 2, 0)
+#define LDPC_SPEC_UNITS(U, X)                                                                                          \
+  U(a, X) U(b, X) U(c, X) U(d, X) U(e, X) U(f, X) U(g, X) U(h, X) U(i, X) U(j, X) U(k, X) U(l, X) U(m, X) U(n, X)      \
+  U(o, X) U(p, X)
+
+/* derived: unit u's graphs, the graphs outside the core, every graph, every unit's name (core first) */
+#define LDPC_SPEC_UNIT_GRAPHS_(u, X) LDPC_SPEC_GRAPHS_UNIT_##u(X)
+#define LDPC_SPEC_UNIT_GRAPHS(u, X) LDPC_SPEC_UNIT_GRAPHS_(u, X) /* u may be a macro (LDPC_SPEC_UNIT) */
+#define LDPC_SPEC_GRAPHS_UNITS(X) LDPC_SPEC_UNITS(LDPC_SPEC_UNIT_GRAPHS, X)
+#define LDPC_SPEC_GRAPHS(X) LDPC_SPEC_GRAPHS_CORE(X) LDPC_SPEC_GRAPHS_UNITS(X)
+#define LDPC_KERNEL_UNITS(U) U(core, 0) LDPC_SPEC_UNITS(U, 0)
+
+#define LDPC_SPEC_COUNT(id, bg, z, ils) +1
+#define LDPC_SPEC_UNIT_COUNT(u, X) +1
+#define LDPC_SPEC_UNIT_SIZE(u, X) (0 LDPC_SPEC_GRAPHS_UNIT_##u(LDPC_SPEC_COUNT)),
+constexpr int NOF_CORE_SPECS   = 0 LDPC_SPEC_GRAPHS_CORE(LDPC_SPEC_COUNT); /* ids [0, 10): bodies of the mixed kernel */
+constexpr int NOF_KERNEL_UNITS = 0 LDPC_KERNEL_UNITS(LDPC_SPEC_UNIT_COUNT); /* core and a..p */
+constexpr int NOF_SPECS        = 0 LDPC_SPEC_GRAPHS(LDPC_SPEC_COUNT);
+/* graphs per unit, in unit (and so id) order: core, a..p (ldpc_graph.cpp spec_unit) */
+constexpr int k_unit_sizes[] = {NOF_CORE_SPECS, LDPC_SPEC_UNITS(LDPC_SPEC_UNIT_SIZE, 0)};
+static_assert(NOF_CORE_SPECS == 10 && sizeof(k_unit_sizes) / sizeof(k_unit_sizes[0]) == NOF_KERNEL_UNITS, "unit table");
+#undef LDPC_SPEC_UNIT_SIZE
+#undef LDPC_SPEC_UNIT_COUNT
+#undef LDPC_SPEC_COUNT
 
 /* A translation unit may define LDPC_SPEC_TU_GRAPHS to the list of the graphs it instantiates before including this
  * header: the schedules of the other graphs are then not evaluated (the constexpr evaluation of one schedule costs
@@ -505,9 +527,19 @@ constexpr int NOF_CORE_SPECS = 10; /* ids [0, 10): bodies of the mixed kernel */
 LDPC_SPEC_TU_GRAPHS(LDPC_SPEC_DEFINE)
 #undef LDPC_SPEC_DEFINE
 
-#define LDPC_SPEC_COUNT(id, bg, z, ils) +1
-constexpr int NOF_SPECS = 0 LDPC_SPEC_GRAPHS(LDPC_SPEC_COUNT);
-#undef LDPC_SPEC_COUNT
+#define LDPC_SPEC_ID(id, bg, z, ils) id,
+constexpr int k_spec_ids[] = {LDPC_SPEC_GRAPHS(LDPC_SPEC_ID)};
+#undef LDPC_SPEC_ID
+constexpr bool spec_ids_in_order()
+{
+  for (int i = 0; i < NOF_SPECS; ++i) {
+    if (k_spec_ids[i] != i) {
+      return false;
+    }
+  }
+  return true;
+}
+static_assert(spec_ids_in_order(), "a graph's id is its position in LDPC_SPEC_GRAPHS");
 
 #ifdef LDPC_SPEC_ALL_GRAPHS
 #define LDPC_SPEC_PTR(id, bg, z, ils) &k_spec##id,

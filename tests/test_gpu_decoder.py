@@ -219,16 +219,18 @@ def test_c2_batch_128_bit_exact_sample(hip_ctx):
         np.testing.assert_array_equal(out[i * out_stride:i * out_stride + 1056], eo, err_msg=f"cb {i}")
 
 
-def _run_plan(hip_ctx, cc, cases):
-    """cases: list of (bg, Z, iters, crc, F, llr). One DecodePlan over all of them; returns (out bytes, results)."""
+def _run_plan(hip_ctx, cc, cases, llr_skew=None):
+    """cases: list of (bg, Z, iters, crc, F, llr). One DecodePlan over all of them; returns (out bytes, results).
+    Each codeblock's LLRs start at a multiple of 16 bytes, plus llr_skew[i] when given."""
     import torch
     specs, offs = [], []
     llr_off = out_off = 0
-    for (bg, Z, it, crc, F, llr) in cases:
+    for i, (bg, Z, it, crc, F, llr) in enumerate(cases):
+        skew = llr_skew[i] if llr_skew is not None else 0
         mode = cc.CRC_MODE_NONE if crc == O.NO_CRC else cc.CRC_MODE_EARLY_STOP
-        specs.append(cc.cb_decode_spec(bg, Z, llr.size, it, mode, HIP_CRC[crc], F, 0.8, llr_off, out_off))
-        offs.append(llr_off)
-        llr_off += (llr.size + 15) // 16 * 16
+        specs.append(cc.cb_decode_spec(bg, Z, llr.size, it, mode, HIP_CRC[crc], F, 0.8, llr_off + skew, out_off))
+        offs.append(llr_off + skew)
+        llr_off += (skew + llr.size + 15) // 16 * 16
         out_off += (cc.message_bytes(bg, Z) + 15) // 16 * 16
     h_llr = np.zeros(llr_off, dtype=np.int8)
     for off, c in zip(offs, cases):
@@ -358,6 +360,57 @@ def test_every_lifted_graph_generic_kernel():
         test_every_lifted_graph(ctx)
     finally:
         ctx.close()
+
+
+_UNALIGNED = {}
+
+
+def _unaligned_cases():
+    """test_prologue_load_paths' codeblocks and their oracle results, built once for both bodies."""
+    if not _UNALIGNED:
+        rng = np.random.default_rng(316)
+        kinds = []
+        # BG1 Z=384 at full length (2Z and L multiples of 16); BG2 Z=36 (2Z = 72); BG1 Z=7 (odd: 2-byte LDS writes);
+        # BG2 Z=208 shortened to a length that is no multiple of 16. CRC early stop on two of them, none on the others.
+        kinds.append((1, 384, 4, O.NO_CRC, random_llrs(rng, O.BG_N_SHORT[1] * 384, "mixed")))
+        kinds.append((2, 36, 3, O.NO_CRC, random_llrs(rng, O.BG_N_SHORT[2] * 36, "mixed")))
+        kinds.append((1, 7, 4, O.CRC16, codeword_llrs(rng, 1, 7, 2.0, 0.9, crc=O.CRC16)[0]))
+        kinds.append((2, 208, 4, O.CRC24B, codeword_llrs(rng, 2, 208, 2.0, 1.25, crc=O.CRC24B)[0][:50 * 208 - 5]))
+        assert (2 * 36) % 16 != 0 and kinds[0][4].size % 16 == 0 and kinds[3][4].size % 16 != 0
+        cases, skew = [], []
+        for (bg, Z, it, crc, llr) in kinds:  # each codeblock at an offset = 0 and at an offset = 3 (mod 16)
+            for sk in (0, 3):
+                cases.append((bg, Z, it, crc, 0, llr))
+                skew.append(sk)
+        _UNALIGNED["cases"], _UNALIGNED["skew"] = cases, skew
+        _UNALIGNED["expect"] = [O.ldpc_decode(bg, Z, llr, it, crc, F) for (bg, Z, it, crc, F, llr) in cases]
+    return _UNALIGNED["cases"], _UNALIGNED["skew"], _UNALIGNED["expect"]
+
+
+@pytest.mark.parametrize("body", ["specialised", "generic"])
+def test_prologue_load_paths(body):
+    """The prologue's three LLR load paths in both decoder bodies: codeblocks whose LLRs start at a multiple of 16 bytes
+    (16-byte loads stored whole when 2Z and the length are multiples of 16, else through 4- or 2-byte LDS writes with a
+    byte-wise tail) and 3 bytes after one (byte-wise loads). One plan per body: every graph on its specialised kernel
+    (one launch per group, LDPC_HIP_LAUNCH_NO_MIXED) or on the generic kernel (LDPC_HIP_LAUNCH_NO_SPEC). Message, CRC
+    flag and iteration count equal the oracle's."""
+    from srsran_projectvtlmo_amd import _lib
+    cc = _cc()
+    cases, skew, expect = _unaligned_cases()
+    ctx = _flag_ctx(_lib.LAUNCH_NO_MIXED if body == "specialised" else _lib.LAUNCH_NO_SPEC)
+    try:
+        if body == "specialised":
+            assert all(cc.specialised(c[0], c[1]) == 1 for c in cases)
+        specs, out, res = _run_plan(ctx, cc, cases, llr_skew=skew)
+    finally:
+        ctx.close()
+    assert sorted({s.llr_offset % 16 for s in specs}) == [0, 3]
+    for i, (s, (bg, Z, it, crc, F, llr), (eo, er)) in enumerate(zip(specs, cases, expect)):
+        nb = cc.message_bytes(bg, Z)
+        np.testing.assert_array_equal(out[s.out_offset:s.out_offset + nb], eo, err_msg=f"cb {i} BG{bg} Z={Z}")
+        assert (res[i, 0] == 1) == (er is not None), f"cb {i} BG{bg} Z={Z}"
+        # without a CRC pass the decoder runs every iteration (ldpc_decoder_impl.cpp:116-146)
+        assert res[i, 1] == (er if er is not None else it), f"cb {i} BG{bg} Z={Z}"
 
 
 def test_narrow_schedule_every_graph():
