@@ -92,6 +92,16 @@ __device__ __forceinline__ void wr8(uint32_t base, uint32_t imm, uint32_t v)
 }
 /* +infinity (the dummy position of an odd row, the scratch column) */
 constexpr int SOFT_INF = 121;
+
+/* pack the two sign-extended soft bits of an edge pair: [lo.b0, lo.b1, hi.b0, hi.b1]. One half-rate v_perm_b32. The
+ * alternative without it, ds_read_i8_d16 / ds_read_i8_d16_hi (each zeroes the other half with SRAM ECC on) and one
+ * full-rate v_or_b32, was built and lost: the compiler does not emit d16 loads for this target, and as inline asm with
+ * their own s_waitcnt lgkmcnt(0) they are a block that the address arithmetic and the first pair's pass 1 no longer
+ * overlap with (C2 +3 us, BG1 Z=128 +6.7 us against this form, profiles/r10/ab_pair_pack.txt). */
+__device__ __forceinline__ uint32_t pack_pair(int lo, int hi)
+{
+  return __builtin_amdgcn_perm(static_cast<uint32_t>(hi), static_cast<uint32_t>(lo), 0x05040100U);
+}
 /* the two-minimum scan's start: 120 (strict <: infinity and +-120 never change it) */
 constexpr unsigned MIN_START = 120U;
 
@@ -140,27 +150,43 @@ __device__ __forceinline__ void pass2(uint32_t G, uint32_t A, s16x2 N1, s16x2 CC
   Cnew           = bits(pf * g);
 }
 
-/* the row's pass-2 constants: n = round(0.8 m) = (52432 m + 26216) >> 16 exactly for m in [0, 120] (gen.cpp:70-79
- * with sf = 0.8f), CC = n2 + m1, PP = the check node's sign, +-1 */
-__device__ __forceinline__ void row_consts(uint32_t m1, uint32_t m2, uint32_t sx, s16x2& N1, s16x2& CC, s16x2& PP)
+/* the row's pass-2 constants as the words they are computed in: n = round(0.8 m) = (52432 m + 26216) >> 16 exactly for
+ * m in [0, 120] (gen.cpp:70-79 with sf = 0.8f), cc = n2 + m1, and the check node's sign pp = +-1, which is valid in its
+ * low half only (fold_halves). pass2 reads them through lo_splat (the packed instructions' op_sel: no instruction),
+ * ext_update reads their low halves directly. */
+__device__ __forceinline__ void row_consts(uint32_t m1, uint32_t m2, uint32_t sx, uint32_t& n1, uint32_t& cc, uint32_t& pp)
 {
-  const uint32_t n1 = (__umul24(m1, 52432U) + 26216U) >> 16;
+  n1                = (__umul24(m1, 52432U) + 26216U) >> 16;
   const uint32_t n2 = (__umul24(m2, 52432U) + 26216U) >> 16;
-  N1                = splat(static_cast<int>(n1));
-  CC                = splat(static_cast<int>(n2 + m1));
-  PP                = splat(static_cast<short>(sx | 1U));
+  cc                = n2 + m1;
+  pp                = sx;
+}
+__device__ __forceinline__ s16x2 lo_splat(uint32_t w) { return splat(static_cast<short>(w)); }
+
+/* full-rate 16-bit minimum of two words' low halves (the upper half of the result is zero); the compiler's own choice
+ * for a three-way minimum is a shift, the half-rate v_min3_u16 and a mask */
+__device__ __forceinline__ uint32_t min_lo16(uint32_t a, uint32_t b)
+{
+  uint32_t r;
+  asm("v_min_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
 }
 
 /* The check node's two minima and parity from the per-half ones: min1 = min(A, B), min2 = min(min2_A, min2_B,
  * max(min1_A, min1_B)) -- the two smallest of the multiset, as the sequential scan finds them. Parity: each half of SX
- * is the XOR of +-1 values (0x0001 / 0xffff), so bits 1-15 of lo ^ hi all equal the parity of the negative signs and
- * (lo ^ hi) | 1 is the check node's sign, +-1, in the low 16 bits (one shift, XOR and OR per row; the bit-31 form
- * took a shift more). */
+ * is the XOR of +-1 values (0x0001 / 0xffff), so bits 1-15 of lo ^ hi all equal the parity of the negative signs, and
+ * bit 0 the parity of the number of values. A row that XORed an odd number of them (an extension edge's sign and its
+ * pairs) has the check node's sign, +-1, in the low 16 bits of sx as it is; any other row ORs 1 into it (sign_word). */
 __device__ __forceinline__ void fold_halves(u16x2 M1, u16x2 M2, uint32_t SX, uint32_t& m1, uint32_t& m2, uint32_t& sx)
 {
   m1 = __builtin_elementwise_min(M1.x, M1.y);
-  m2 = __builtin_elementwise_min(__builtin_elementwise_min(M2.x, M2.y), __builtin_elementwise_max(M1.x, M1.y));
+  m2 = min_lo16(__builtin_elementwise_min(M2.x, M2.y), __builtin_elementwise_max(M1.x, M1.y));
   sx = SX ^ (SX >> 16);
+}
+template <bool ODD>
+__device__ __forceinline__ uint32_t sign_word(uint32_t sx)
+{
+  return ODD ? sx : (sx | 1U);
 }
 
 /* Merge of a split row's halves (lanes l and l ^ 32) through v_permlane32_swap: after the swap each lane holds its
@@ -251,49 +277,13 @@ struct dec {
    * overflows, and +-infinity with the same sign from then on, so no soft bit and no c2v are kept for the edge and
    * nothing is written back: after the iterations nothing reads an extension column from LDS (the hard decision and
    * the early-stop check read soft[0, K Z) only; grep s_soft).
-   * Every operation is a full-rate 32-bit or 16-bit VOP2 (tools/ubench/README.md): no compare / select. The 16-bit
-   * forms read the low halves of their sources and zero the high half of their result. */
-  /* 120 is a 32-bit literal of the instruction (2.6 against 2.1 cycles): the kernel has no SGPR to spare for it */
-  static __device__ __forceinline__ uint32_t min120_u16(uint32_t x)
-  {
-    uint32_t r;
-    asm("v_min_u16_e32 %0, 0x78, %1" : "=v"(r) : "v"(x));
-    return r;
-  }
-  static __device__ __forceinline__ uint32_t max_i16(uint32_t a, uint32_t b)
-  {
-    uint32_t r;
-    asm("v_max_i16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-  }
-  static __device__ __forceinline__ uint32_t add_u16(uint32_t a, uint32_t b)
-  {
-    uint32_t r;
-    asm("v_add_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-  }
-  static __device__ __forceinline__ uint32_t sub_u16(uint32_t a, uint32_t b) /* a - b */
-  {
-    uint32_t r;
-    asm("v_sub_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-  }
-  static __device__ __forceinline__ uint32_t sub120_u16(uint32_t b) /* 120 - b */
-  {
-    uint32_t r;
-    asm("v_sub_u16_e32 %0, 0x78, %1" : "=v"(r) : "v"(b));
-    return r;
-  }
+   * No compare and no select: 16-bit and 32-bit VOP2 operations, left to the compiler where it picks them itself. */
+  /* full rate; the compiler fuses the product into a 64-bit multiply-add otherwise. Reads the low halves of its
+   * sources and zeroes the high half of its result. */
   static __device__ __forceinline__ uint32_t mul_u16(uint32_t a, uint32_t b)
   {
     uint32_t r;
     asm("v_mul_lo_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-  }
-  static __device__ __forceinline__ uint32_t hi8_u16(uint32_t a) /* the low half's upper byte */
-  {
-    uint32_t r;
-    asm("v_lshrrev_b16_e32 %0, 8, %1" : "=v"(r) : "v"(a));
     return r;
   }
 
@@ -329,24 +319,34 @@ struct dec {
   {
     ext_init(cr, L, std::make_integer_sequence<int, G.n_steps>{});
   }
-  /* The extension edge as the first edge of the two-minimum scan (start 120, strict <): M1.lo = min(a, 120), M2 stays
-   * at its start (an infinite edge moves neither), and the parity starts at g. */
-  static __device__ __forceinline__ void ext_seed(uint32_t X, u16x2& M1, u16x2& M2, uint32_t& SX)
+  /* The extension edge in the row's scan. Its sign starts the parity (ext_seed); its magnitude joins the two minima
+   * after the fold (ext_fold: the two smallest of a multiset do not depend on the order), as min(a, 120): an infinite
+   * edge moves neither minimum. Seeding the packed scan with it instead (M1.lo = min(a, 120)) took the first pair's
+   * shortcut away (a scan from the start value is one packed minimum, from a seed three) and two 32-bit literals. */
+  static __device__ __forceinline__ void ext_seed(uint32_t X, uint32_t& SX) { SX = X >> 16; }
+  static __device__ __forceinline__ void ext_fold(uint32_t X, uint32_t& m1, uint32_t& m2)
   {
-    M1 = as_u(min120_u16(X) | (static_cast<uint32_t>(LLR_MAX) << 16));
-    M2 = splatu(MIN_START);
-    SX = X >> 16;
+    using u16 = unsigned short;
+    const u16 a = __builtin_elementwise_min(static_cast<u16>(X), static_cast<u16>(MIN_START));
+    m2          = __builtin_elementwise_min(static_cast<u16>(m2), __builtin_elementwise_max(static_cast<u16>(m1), a));
+    m1          = __builtin_elementwise_min(static_cast<u16>(m1), a);
   }
-  /* The visit's update from the row's pass-2 constants (row_consts: n1, n2 + m1 and P = +-1, read from the low halves
-   * of the packed words, so no register beyond pass 2's): f = max(n1, n2 + m1 - a), u = a + P f, and a becomes
-   * infinite when u >= 121, i.e. when promotion_sum(c2v', v2c) overflows (pass2's note; an infinite a gives f = n1 and
-   * u >= 145, so it stays). The overflow ORs 255 into a, and a marker of 255 behaves like ext_state's 241 in every
-   * use: min(a, 120) = 120, n2 + m1 - a < 0 <= n1, u >= 145. */
-  static __device__ __forceinline__ void ext_update(uint32_t& X, s16x2 N1, s16x2 CC, s16x2 PP)
+  /* The visit's update from the row's pass-2 constants (row_consts: n1, n2 + m1 and P = +-1, the low halves of the
+   * words row_consts leaves: no register beyond pass 2's and no splat): f = max(n1, n2 + m1 - a), u = a + P f, and a
+   * becomes infinite when u >= 121, i.e. when promotion_sum(c2v', v2c) overflows (pass2's note; an infinite a gives
+   * f = n1 and u >= 145, so it stays). The overflow ORs 255 into a, and a marker of 255 behaves like ext_state's 241
+   * in every use: min(a, 120) = 120, n2 + m1 - a < 0 <= n1, u >= 145.
+   * Plain 16-bit arithmetic but for the product: operations the compiler sees need no s_nop between them (after an
+   * inline-asm result it inserts one before every dependent use), and it takes n1 from the high half of its
+   * multiply-add by SDWA instead of shifting it down. */
+  static __device__ __forceinline__ void ext_update(uint32_t& X, uint32_t n1, uint32_t cc, uint32_t pp)
   {
-    const uint32_t f = max_i16(bits(N1), sub_u16(bits(CC), X));
-    const uint32_t u = add_u16(X, mul_u16(f, bits(PP)));
-    X |= hi8_u16(sub120_u16(u)); /* 120 - u is in [-231, 216]: upper byte 0xff when negative, else 0 */
+    const unsigned short a  = static_cast<unsigned short>(X);
+    const short          f  = __builtin_elementwise_max(static_cast<short>(n1), static_cast<short>(cc - a));
+    const uint32_t       pf = mul_u16(static_cast<uint32_t>(static_cast<unsigned short>(f)), pp);
+    const unsigned short u  = static_cast<unsigned short>(a + pf);
+    /* 120 - u is in [-231, 216]: upper byte 0xff when negative, else 0 */
+    X |= static_cast<uint32_t>(static_cast<unsigned short>(120 - u) >> 8);
   }
 
   /* A row's pass-1 state kept in registers across the step barrier (pipelined single-row chains, ldpc_spec.h):
@@ -456,13 +456,12 @@ struct dec {
     });
     u16x2    M1 = splatu(MIN_START), M2 = splatu(MIN_START);
     uint32_t SX = 0;
-    if constexpr (ro.xe >= 0) { /* the scan starts with the extension edge kept in a register */
-      ext_seed(cr[Q0 + NP], M1, M2, SX);
+    if constexpr (ro.xe >= 0) { /* the parity starts with the sign of the extension edge kept in a register */
+      ext_seed(cr[Q0 + NP], SX);
     }
     static_for<NE>([&](auto ic) __attribute__((always_inline)) {
-      constexpr int  i  = decltype(ic)::value;
-      const uint32_t sx = __builtin_amdgcn_perm(static_cast<uint32_t>(hi[i]), static_cast<uint32_t>(lo[i]), 0x05040100U);
-      pass1(sx, cr[Q0 + i], M1, M2, SX, cy.gs[i], cy.a[i], L.one2);
+      constexpr int i = decltype(ic)::value;
+      pass1(pack_pair(lo[i], hi[i]), cr[Q0 + i], M1, M2, SX, cy.gs[i], cy.a[i], L.one2);
     });
     cy.m1 = M1;
     cy.m2 = M2;
@@ -487,8 +486,8 @@ struct dec {
     int      lo[NP], hi[NP];
     u16x2    M1 = splatu(MIN_START), M2 = splatu(MIN_START);
     uint32_t SX = 0;
-    if constexpr (ro.xe >= 0 && NE == 0) { /* with early pairs, role_early seeded the scan */
-      ext_seed(cr[Q0 + NP], M1, M2, SX);
+    if constexpr (ro.xe >= 0 && NE == 0) { /* with early pairs, role_early seeded the parity */
+      ext_seed(cr[Q0 + NP], SX);
     }
     if constexpr (NE > 0) {
       M1 = cy.m1;
@@ -521,8 +520,7 @@ struct dec {
     });
     static_for<NP - NE>([&](auto ic) __attribute__((always_inline)) {
       constexpr int i = NE + decltype(ic)::value;
-      /* pack the two sign-extended bytes: [lo.b0, lo.b1, hi.b0, hi.b1] */
-      Sx[i] = __builtin_amdgcn_perm(static_cast<uint32_t>(hi[i]), static_cast<uint32_t>(lo[i]), 0x05040100U);
+      Sx[i] = pack_pair(lo[i], hi[i]);
       if constexpr (i == NE) {
         SPEC_STAMP_FULL(S, 1);
       }
@@ -534,9 +532,20 @@ struct dec {
     if constexpr (ro.p == 2) {
       merge_partner(m1, m2, sx);
     }
-    s16x2 N1, CC, PP; /* n = round(0.8 m) (gen.cpp:70-79 with sf = 0.8f), n2 + m1, the sign parity */
-    row_consts(m1, m2, sx, N1, CC, PP);
+    if constexpr (ro.xe >= 0) {
+      ext_fold(cr[Q0 + NP], m1, m2);
+    }
+    /* n = round(0.8 m) (gen.cpp:70-79 with sf = 0.8f), n2 + m1, the sign parity; a row with an extension edge has
+     * XORed 2 NP + 1 signs */
+    uint32_t n1w, ccw, ppw;
+    row_consts(m1, m2, sign_word<ro.xe >= 0 && ro.p == 1>(sx), n1w, ccw, ppw);
+    const s16x2 N1 = lo_splat(n1w), CC = lo_splat(ccw), PP = lo_splat(ppw);
     SPEC_STAMP_FULL(S, 3);
+    /* no soft bit and no c2v for the extension edge: its sticky infinity only. Its dependent operations come first
+     * in program order: after the last pair's writes they were a chain of s_nop, one per operation */
+    if constexpr (ro.xe >= 0) {
+      ext_update(cr[Q0 + NP], n1w, ccw, ppw);
+    }
     /* Graphs with one wave per row group (Z <= 64): every pair's pass 2 before any of its writes, so the scheduler
      * can interleave the pairs' chains (a packed op reading the previous one's result otherwise waits an s_nop); the
      * step is a latency chain there (BG2 Z=36: 65.8 -> 63.5 us per 128-CB batch). Larger graphs keep pass 2 and the
@@ -563,9 +572,6 @@ struct dec {
         wr8(base[2 * i + 1], i1, sn >> 16);
       }
     });
-    if constexpr (ro.xe >= 0) { /* no soft bit and no c2v for the extension edge: its sticky infinity only */
-      ext_update(cr[Q0 + NP], N1, CC, PP);
-    }
   }
 
   /* Wave priority (s_setprio) on graphs with W >= 3 waves per group: in a pipelined chain the group completing a row
@@ -904,9 +910,8 @@ struct qdec {
     u16x2    M1 = splatu(MIN_START), M2 = splatu(MIN_START);
     uint32_t SX = 0;
     static_for<NP>([&](auto ic) __attribute__((always_inline)) {
-      constexpr int  i  = decltype(ic)::value;
-      const uint32_t sx = __builtin_amdgcn_perm(static_cast<uint32_t>(hi[i]), static_cast<uint32_t>(lo[i]), 0x05040100U);
-      pass1(sx, cr[Q0 + i], M1, M2, SX, Gs[i], A[i], L.one2);
+      constexpr int i = decltype(ic)::value;
+      pass1(pack_pair(lo[i], hi[i]), cr[Q0 + i], M1, M2, SX, Gs[i], A[i], L.one2);
     });
     uint32_t m1, m2, sx;
     fold_halves(M1, M2, SX, m1, m2, sx);
@@ -919,8 +924,9 @@ struct qdec {
     }
     static_assert(ro.P == 2 || ro.P == 4 || ro.P == 8, "lanes per check node");
     SPEC_STAMP_FULL(S, 2);
-    s16x2 N1, CC, PP; /* round(0.8 m), gen.cpp:70-79; n2 + m1; the sign parity */
-    row_consts(m1, m2, sx, N1, CC, PP);
+    uint32_t n1w, ccw, ppw; /* round(0.8 m), gen.cpp:70-79; n2 + m1; the sign parity */
+    row_consts(m1, m2, sign_word<false>(sx), n1w, ccw, ppw);
+    const s16x2 N1 = lo_splat(n1w), CC = lo_splat(ccw), PP = lo_splat(ppw);
     SPEC_STAMP_FULL(S, 3);
     uint32_t snv[NP];
     static_for<NP>([&](auto ic) __attribute__((always_inline)) {
