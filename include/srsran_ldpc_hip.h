@@ -431,6 +431,50 @@ int ldpc_hip_dematch_decode_scr_launch(ldpc_hip_plan* plan, const ldpc_hip_demat
                                        const ldpc_hip_scramble_desc* scr, int8_t* d_soft, uint8_t* d_out,
                                        ldpc_hip_cb_result* d_results, void* stream);
 
+/* ---- modulation mapper: PDSCH scrambling and mapping of rate-matched bits ----------
+ * modulation_mapper::modulate (include/srsran/phy/upper/channel_modulation/modulation_mapper.h,
+ * modulation_mapper_lut_impl.cpp): symbol i takes input bits Qm i .. Qm i + Qm - 1 (packed MSB first), s_k = 1 - 2 b_k,
+ * Re from the even-index bits and Im from the odd ones in the nested form of TS 38.211 5.1 (QPSK (s0, s1), 16-QAM
+ * (s0 (2 - s2), s1 (2 - s3)), 64-QAM (s0 (4 - s2 (2 - s4)), ..), 256-QAM (s0 (8 - s2 (4 - s4 (2 - s6))), ..), BPSK
+ * (s0, s0), pi/2-BPSK (s0, s0) at even symbols of the span and (-s0, s0) at odd ones). The ci8 output is these odd
+ * integers, to be scaled by ldpc_hip_modulation_scaling; the cf32 output is float(level) * scaling in one float32
+ * multiply, the reference's table bit for bit. pdsch_modulator_impl.cpp:30-50, 108-132 scrambles the codeword with
+ * c_init = (rnti << 15) + (q << 14) + n_id before it maps it: `scramble` does that on the way. */
+#define LDPC_HIP_SYM_CF32 0   /* interleaved float re, im  (span<cf_t>)  */
+#define LDPC_HIP_SYM_CI8  1   /* interleaved int8 re, im   (span<ci8_t>) */
+/* modulation_mapper::get_modulation_scaling: 1/sqrt(2) for (pi/2-)BPSK and QPSK, sqrtf(1.0f / 10), sqrtf(1.0f / 42),
+ * sqrtf(1.0f / 170) for 16/64/256-QAM. Host only; 0.0f for a value that is no scheme. */
+float ldpc_hip_modulation_scaling(int modulation);
+/* One segment: nof_symbols symbols of one scheme from nof_symbols * Qm packed bits. For pi/2-BPSK the symbol parity
+ * counts from the segment's first symbol, as in the reference span. */
+typedef struct {              /* 40 bytes */
+  uint64_t bit_offset;        /* bytes from d_bits (unused by the fused launch)        */
+  uint64_t symbol_offset;     /* symbols from d_symbols                                 */
+  uint64_t seq_offset;        /* first sequence bit                                     */
+  uint32_t nof_symbols;
+  uint32_t c_init;
+  uint8_t  modulation;        /* LDPC_HIP_MOD_*                                         */
+  uint8_t  scramble;          /* 0: map the bits as they are (c_init 0 is a legal seed) */
+  uint8_t  pad[6];
+} ldpc_hip_mod_desc;
+/* Maps nof_segs segments on device buffers, asynchronously on `stream` (NULL = the context stream). d_symbols holds
+ * `format` elements (2 or 8 bytes per symbol) and is aligned for them; segments whose first symbol lies on a 16-byte
+ * boundary take vector stores. Any input byte offset; no byte past a segment's last input byte is read and none
+ * outside its symbols written. Segments must not overlap; a segment holds fewer than 2^31 symbols. */
+int ldpc_hip_modulate_launch(ldpc_hip_ctx* ctx, uint32_t nof_segs, const ldpc_hip_mod_desc* descs,
+                             const uint8_t* d_bits, void* d_symbols, int format, void* stream);
+/* modulation_mapper::modulate of one span on host buffers (no scrambling). */
+int ldpc_hip_modulate_sync(ldpc_hip_ctx* ctx, uint32_t nof_symbols, int modulation, const uint8_t* bits, void* symbols,
+                           int format);
+/* Rate matching, scrambling and mapping in one launch: ldpc_hip_rate_match_launch of descs (out_offset unused) whose
+ * E bits never reach memory but go, scrambled by mod[i], to mod[i].nof_symbols symbols at mod[i].symbol_offset.
+ * Requires mod[i].nof_symbols * Qm == descs[i].rm_length < 2^31 and a scheme whose bits per symbol equal
+ * descs[i].modulation_order; pi/2-BPSK is refused (PDSCH has no such scheme, and a span per codeblock would restart
+ * the symbol parity). A codeblock's seq_offset is the sum of the codeword's earlier rm_length. */
+int ldpc_hip_rate_match_modulate_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldpc_hip_rm_desc* descs,
+                                        const ldpc_hip_mod_desc* mod, const uint8_t* d_cws, void* d_symbols,
+                                        int format, void* stream);
+
 /* ---- launch graphs: one submission per slot ---------------------------------------------------------------- */
 /* srsRAN runs the PUSCH decode chain once per slot with the same shape slot after slot (pusch_decoder_impl /
  * pusch_decoder_hw_impl call the decoder per codeblock and join per TB). Here the chain's *_launch calls on `stream`

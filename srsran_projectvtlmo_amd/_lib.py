@@ -40,7 +40,10 @@ EXPORTED_SYMBOLS = [
     "ldpc_hip_decode_work", "ldpc_hip_auto_min_work",
     "ldpc_hip_prs_init", "ldpc_hip_descramble_launch", "ldpc_hip_scramble_bits_launch", "ldpc_hip_descramble_sync",
     "ldpc_hip_rate_dematch_scr_launch", "ldpc_hip_dematch_decode_scr_launch",
+    "ldpc_hip_modulation_scaling", "ldpc_hip_modulate_launch", "ldpc_hip_modulate_sync",
+    "ldpc_hip_rate_match_modulate_launch",
 ]
+SYM_CF32, SYM_CI8 = 0, 1   # LDPC_HIP_SYM_*
 HARQ_STRIDE = 25344   # LDPC_HIP_HARQ_STRIDE
 
 
@@ -148,6 +151,16 @@ class ScrambleDesc(ctypes.Structure):
 assert ctypes.sizeof(PrsState) == 8 and ctypes.sizeof(PrsSeg) == 32 and ctypes.sizeof(ScrambleDesc) == 16
 
 
+class ModDesc(ctypes.Structure):
+    """ldpc_hip_mod_desc (include/srsran_ldpc_hip.h)."""
+    _fields_ = [("bit_offset", ctypes.c_uint64), ("symbol_offset", ctypes.c_uint64), ("seq_offset", ctypes.c_uint64),
+                ("nof_symbols", ctypes.c_uint32), ("c_init", ctypes.c_uint32), ("modulation", ctypes.c_uint8),
+                ("scramble", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 6)]
+
+
+assert ctypes.sizeof(ModDesc) == 40
+
+
 class TbResult(ctypes.Structure):
     _fields_ = [("tb_crc_ok", ctypes.c_uint8), ("written", ctypes.c_uint8), ("nof_cbs_ok", ctypes.c_uint16)]
 
@@ -223,6 +236,11 @@ def load():
         "ldpc_hip_dematch_decode_scr_launch": (I, [P, ctypes.POINTER(DematchDesc), P, ctypes.POINTER(ctypes.c_uint64),
                                                    ctypes.POINTER(DemodDesc), P, P, ctypes.POINTER(ScrambleDesc), P,
                                                    P, P, P]),
+        "ldpc_hip_modulation_scaling": (ctypes.c_float, [I]),
+        "ldpc_hip_modulate_launch": (I, [P, U32, ctypes.POINTER(ModDesc), P, P, I, P]),
+        "ldpc_hip_modulate_sync": (I, [P, U32, I, P, P, I]),
+        "ldpc_hip_rate_match_modulate_launch": (I, [P, U32, ctypes.POINTER(RmDesc), ctypes.POINTER(ModDesc), P, P, I,
+                                                    P]),
         "ldpc_hip_capture_begin": (I, [P, P]),
         "ldpc_hip_capture_end": (I, [P, P, ctypes.POINTER(P)]),
         "ldpc_hip_graph_launch": (I, [P, P]),

@@ -180,8 +180,19 @@ public:
 std::shared_ptr<ldpc_decoder_factory>        create_ldpc_decoder_factory_sw(const std::string& dec_type);
 std::shared_ptr<ldpc_rate_dematcher_factory> create_ldpc_rate_dematcher_factory_sw(const std::string& dematcher_type);
 
-/* demodulation_mapper.h:46-70, channel_modulation_factories.h:32-39 (the EVM calculator is outside the path) */
-using cf_t = std::complex<float>;
+/* modulation_mapper.h:35-64, demodulation_mapper.h:46-70, channel_modulation_factories.h:32-39 (the EVM calculator is
+ * outside the path); complex.h:44 */
+using cf_t  = std::complex<float>;
+using ci8_t = std::complex<int8_t>;
+class modulation_mapper
+{
+public:
+  /* in srsRAN the library's own (modulation_mapper_lut_impl.cpp); out of tree ldpc_hip_adapters.cpp defines it */
+  static float get_modulation_scaling(modulation_scheme scheme);
+  virtual ~modulation_mapper() = default;
+  virtual void  modulate(span<cf_t> symbols, const bit_buffer& input, modulation_scheme scheme)  = 0;
+  virtual float modulate(span<ci8_t> symbols, const bit_buffer& input, modulation_scheme scheme) = 0;
+};
 class demodulation_mapper
 {
 public:
@@ -200,6 +211,7 @@ class channel_modulation_factory
 {
 public:
   virtual ~channel_modulation_factory()                                     = default;
+  virtual std::unique_ptr<modulation_mapper>   create_modulation_mapper()   = 0;
   virtual std::unique_ptr<demodulation_mapper> create_demodulation_mapper() = 0;
   virtual std::unique_ptr<evm_calculator>      create_evm_calculator()      = 0;
 };

@@ -236,6 +236,33 @@ void demodulation_mapper_hip::demodulate_soft(span<log_likelihood_ratio> llrs,
                                     reinterpret_cast<int8_t*>(llrs.data())));
 }
 
+/* ---- modulation mapper ---- */
+#ifndef SRSRAN_LDPC_HIP_IN_TREE
+/* in srsRAN this is the library's own (modulation_mapper_lut_impl.cpp) */
+float modulation_mapper::get_modulation_scaling(modulation_scheme scheme)
+{
+  return ldpc_hip_modulation_scaling(static_cast<int>(scheme));
+}
+#endif
+
+void modulation_mapper_hip::modulate(span<cf_t> symbols, const bit_buffer& input, modulation_scheme scheme)
+{
+  /* modulation_mapper_lut_impl.cpp */
+  srsran_assert(input.size() == get_bits_per_symbol(scheme) * symbols.size(),
+                "The number of bits must be equal to the number of symbols times the bits per symbol.");
+  check_rc(ctx.get(), ldpc_hip_modulate_sync(ctx.get(), static_cast<uint32_t>(symbols.size()), static_cast<int>(scheme),
+                                             input.get_buffer().data(), symbols.data(), LDPC_HIP_SYM_CF32));
+}
+
+float modulation_mapper_hip::modulate(span<ci8_t> symbols, const bit_buffer& input, modulation_scheme scheme)
+{
+  srsran_assert(input.size() == get_bits_per_symbol(scheme) * symbols.size(),
+                "The number of bits must be equal to the number of symbols times the bits per symbol.");
+  check_rc(ctx.get(), ldpc_hip_modulate_sync(ctx.get(), static_cast<uint32_t>(symbols.size()), static_cast<int>(scheme),
+                                             input.get_buffer().data(), symbols.data(), LDPC_HIP_SYM_CI8));
+  return get_modulation_scaling(scheme);
+}
+
 namespace {
 class channel_modulation_factory_hip : public channel_modulation_factory
 {
@@ -243,6 +270,10 @@ public:
   channel_modulation_factory_hip(int dev, std::shared_ptr<channel_modulation_factory> evm) :
     device(dev), evm_source(std::move(evm))
   {
+  }
+  std::unique_ptr<modulation_mapper> create_modulation_mapper() override
+  {
+    return std::make_unique<modulation_mapper_hip>(device);
   }
   std::unique_ptr<demodulation_mapper> create_demodulation_mapper() override
   {

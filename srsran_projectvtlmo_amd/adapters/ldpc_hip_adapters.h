@@ -3,6 +3,7 @@
  *
  *   srsran::ldpc_decoder_hip            : ldpc_decoder         (ldpc_decoder.h:37-75)        factory type "hip"
  *   srsran::ldpc_rate_dematcher_hip     : ldpc_rate_dematcher  (ldpc_rate_dematcher.h:35-56) factory type "hip"
+ *   srsran::modulation_mapper_hip       : modulation_mapper    (modulation_mapper.h:35-64)    channel_modulation_factory
  *   srsran::demodulation_mapper_hip     : demodulation_mapper  (demodulation_mapper.h:46-70)  channel_modulation_factory
  *   srsran::hal::hw_accelerator_pusch_dec_hip : hal::hw_accelerator_pusch_dec (hw_accelerator_pusch_dec.h:83-115)
  *                                                                                       acc_type "mi355x"
@@ -141,7 +142,20 @@ private:
   ldpc_hip_context ctx;
 };
 
-/* channel_modulation_factory whose demodulation mappers run on the GPU; EVM calculators come from `evm_source`
+/* The modulation mapper on the GPU: the reference's float32 table and ci8 levels
+ * (modulation_mapper_lut_impl.cpp) bit for bit, through ldpc_hip_modulate_sync. */
+class modulation_mapper_hip : public modulation_mapper
+{
+public:
+  explicit modulation_mapper_hip(int device = 0) : ctx(device) {}
+  void  modulate(span<cf_t> symbols, const bit_buffer& input, modulation_scheme scheme) override;
+  float modulate(span<ci8_t> symbols, const bit_buffer& input, modulation_scheme scheme) override;
+
+private:
+  ldpc_hip_context ctx;
+};
+
+/* channel_modulation_factory whose modulation and demodulation mappers run on the GPU; EVM calculators come from `evm_source`
  * (e.g. create_channel_modulation_sw_factory()) when given, else nullptr. */
 std::shared_ptr<channel_modulation_factory>
 create_channel_modulation_factory_hip(int device = 0, std::shared_ptr<channel_modulation_factory> evm_source = nullptr);

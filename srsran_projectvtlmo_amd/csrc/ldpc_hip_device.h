@@ -330,6 +330,41 @@ struct demod_seg {
   uint8_t  pad[6];
 };
 
+/* ---- modulation mapper (modulation_mapper_lut_impl.cpp; ldpc_modulation_kernels.hip) ----------------------------------
+ * One segment of ldpc_hip_modulate_launch: nof_symbols symbols of one scheme from packed bits (MSB first). A thread
+ * owns one chunk: MOD_CHUNK_BITS(Qm) bits, a whole number of 32-bit sequence words and of symbols (32 bits, 96 for
+ * 64-QAM). Blocks [block0, block0 + ceil(chunks / MOD_BLOCK)) of the launch work on the segment. x1 == 0: the bits are
+ * mapped as they are (an x1 state is never zero); else (x1, x2) is the generator's state at the segment's first bit. */
+constexpr int MOD_BLOCK = 256;
+constexpr uint32_t mod_chunk_bits(uint32_t qm) { return qm == 6 ? 96U : 32U; }
+struct mod_seg {
+  uint64_t bit_offset;  /* bytes from the bit base (unused by the fused kernel) */
+  uint64_t sym_offset;  /* symbols from the symbol base                         */
+  uint32_t nof_symbols;
+  uint32_t block0;
+  uint32_t x1;
+  uint32_t x2;
+  uint8_t  modulation;  /* modulation_scheme value                              */
+  uint8_t  pad[7];
+};
+/* One codeblock of ldpc_hip_rate_match_modulate_launch: the rate matcher's item (out_offset unused) and the mapper's. */
+struct rm_mod_cb {
+  ratematch_cb rm;
+  mod_seg      mod;
+};
+static_assert(sizeof(mod_seg) == 40 && sizeof(rm_mod_cb) == 88, "modulation work item layout");
+
+/* get_modulation_scaling (modulation_mapper_lut_impl.cpp): the float32 bit patterns of 1/sqrt(2), sqrtf(1.0f / 10),
+ * sqrtf(1.0f / 42), sqrtf(1.0f / 170); 0 (0.0f) for a value that is no scheme. A symbol is float(level) * scaling. */
+constexpr uint32_t mod_scaling_bits(int modulation)
+{
+  return (modulation == 0 || modulation == 1 || modulation == 2) ? 0x3f3504f3U
+         : modulation == 4                                         ? 0x3ea1e89bU
+         : modulation == 6                                         ? 0x3e1e01b3U
+         : modulation == 8                                         ? 0x3d9d130eU
+                                                                   : 0U;
+}
+
 /* Slopes, intercepts and interval widths of the piecewise-linear LLR approximations, computed on the host in float
  * exactly as the reference computes its tables (demodulation_mapper_qam{16,64,256}.cpp), passed by value. */
 struct demod_tables {

@@ -44,6 +44,12 @@ hipError_t launch_demodulate(const demod_seg* d_segs, uint32_t nseg, uint32_t nb
                              const float* d_sym, const float* d_nv, int8_t* d_llr, hipStream_t stream);
 hipError_t launch_prs(const prs_seg* d_segs, uint32_t nseg, uint32_t nblocks, bool bits, const uint8_t* d_in,
                       uint8_t* d_out, hipStream_t stream);
+/* ---- ldpc_modulation_kernels.hip: the modulation mapper, stand-alone and behind the rate matcher; ci8: int8 (re, im)
+ * pairs, else float pairs; nblocks as the items' block0 count them ---- */
+hipError_t launch_modulate(const mod_seg* d_segs, uint32_t nseg, uint32_t nblocks, bool ci8, const uint8_t* d_bits,
+                           void* d_sym, hipStream_t stream);
+hipError_t launch_rate_match_modulate(const rm_mod_cb* d_cbs, uint32_t ncb, uint32_t nblocks, bool ci8,
+                                      const uint8_t* d_cws, void* d_sym, hipStream_t stream);
 /* the persistent work-queue kernels that are not per graph (ldpc_hip_dwq.cpp) */
 const void* dwq_kernel_dematch();
 const void* dwq_kernel_encode();
