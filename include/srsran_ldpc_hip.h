@@ -475,6 +475,47 @@ int ldpc_hip_rate_match_modulate_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, con
                                         const ldpc_hip_mod_desc* mod, const uint8_t* d_cws, void* d_symbols,
                                         int format, void* stream);
 
+/* ---- channel equalizer: received REs and channel estimates to the soft demodulator's inputs --------------------
+ * channel_equalizer::equalize (include/srsran/phy/upper/equalization/channel_equalizer.h,
+ * channel_equalizer_generic_impl.cpp:165-221): the scalar float32 loops of equalize_zf_1xn.h:136-178,
+ * equalize_mmse_1xn.h:56-96 and equalize_zf_2xn.h:58-63, 182-252, operand by operand, so the equalised symbols and the
+ * post-equalisation noise variances are the reference's bit for bit (built without its SIMD loops); an RE the reference
+ * calls abnormal is (0, +inf). Topologies: ZF and MMSE with one layer on 1 to 4 rx ports, ZF with two layers on 2 or
+ * 4 ports. The reference goes up to 16 ports for one layer; 4 is the PUSCH processor's limit and this library's.
+ * Received symbols must be finite; estimates and noise variances may be anything. cbf16 elements are 4 bytes (bf16 re,
+ * bf16 im), and the two cbf16 base pointers are aligned for them. */
+#define LDPC_HIP_EQ_ZF 0
+#define LDPC_HIP_EQ_MMSE 1
+/* Host only: 1 for the ten topologies above, else 0. */
+int ldpc_hip_equalize_supported(int algorithm, uint32_t nof_rx_ports, uint32_t nof_tx_layers);
+/* One segment: nof_re REs of one topology. */
+typedef struct {            /* offsets and strides in cbf16 elements (4 bytes: bf16 re, bf16 im) */
+  uint64_t sym_offset;      /* port 0, RE 0 in d_ch_symbols; port p at + p * sym_stride                  */
+  uint64_t sym_stride;      /* >= nof_re (== nof_re: the reference's re_list tensor)                     */
+  uint64_t est_offset;      /* (port 0, layer 0), RE 0 in d_ch_estimates                                 */
+  uint64_t est_stride;      /* plane (port p, layer l) at + (l * nof_rx_ports + p) * est_stride          */
+  uint64_t out_offset;      /* symbols from d_eq_symbols, floats from d_eq_noise_vars                    */
+  uint32_t nof_re;
+  float    tx_scaling;      /* > 0 */
+  float    noise_var[4];    /* per rx port */
+  uint8_t  algorithm, nof_rx_ports, nof_tx_layers, pad[5];
+} ldpc_hip_eq_desc;
+/* Equalises nof_segs segments on device buffers, asynchronously on `stream` (NULL = the context stream). Segment i
+ * writes nof_re * nof_tx_layers symbols (float re, im) at d_eq_symbols + 2 * out_offset floats and as many variances at
+ * d_eq_noise_vars + out_offset, two layers interleaved per RE (eq[2 i + layer], the reverted layer mapping
+ * ldpc_hip_demodulate_launch expects). Planes on 16-byte (8-byte) boundaries take 16-byte (8-byte) loads, outputs
+ * likewise; no byte outside a segment's planes is read and none outside its outputs written. Segments of different
+ * topologies may share a launch; one with nof_re == 0 is skipped. LDPC_HIP_EINVAL: an unsupported topology, a
+ * tx_scaling that is not > 0 (NaN included), a stride below nof_re, nof_re * nof_tx_layers >= 2^31, a null argument. */
+int ldpc_hip_equalize_launch(ldpc_hip_ctx* ctx, uint32_t nof_segs, const ldpc_hip_eq_desc* descs,
+                             const uint16_t* d_ch_symbols, const uint16_t* d_ch_estimates, float* d_eq_symbols,
+                             float* d_eq_noise_vars, void* stream);
+/* channel_equalizer::equalize of one segment on host buffers: ch_symbols [port][re], ch_estimates [layer][port][re]
+ * (cbf16, contiguous), noise_vars one per port. */
+int ldpc_hip_equalize_sync(ldpc_hip_ctx* ctx, int algorithm, uint32_t nof_re, uint32_t nof_rx_ports,
+                           uint32_t nof_tx_layers, const uint16_t* ch_symbols, const uint16_t* ch_estimates,
+                           const float* noise_vars, float tx_scaling, float* eq_symbols, float* eq_noise_vars);
+
 /* ---- launch graphs: one submission per slot ---------------------------------------------------------------- */
 /* srsRAN runs the PUSCH decode chain once per slot with the same shape slot after slot (pusch_decoder_impl /
  * pusch_decoder_hw_impl call the decoder per codeblock and join per TB). Here the chain's *_launch calls on `stream`

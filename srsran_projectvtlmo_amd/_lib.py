@@ -42,8 +42,10 @@ EXPORTED_SYMBOLS = [
     "ldpc_hip_rate_dematch_scr_launch", "ldpc_hip_dematch_decode_scr_launch",
     "ldpc_hip_modulation_scaling", "ldpc_hip_modulate_launch", "ldpc_hip_modulate_sync",
     "ldpc_hip_rate_match_modulate_launch",
+    "ldpc_hip_equalize_supported", "ldpc_hip_equalize_launch", "ldpc_hip_equalize_sync",
 ]
 SYM_CF32, SYM_CI8 = 0, 1   # LDPC_HIP_SYM_*
+EQ_ZF, EQ_MMSE = 0, 1      # LDPC_HIP_EQ_*
 HARQ_STRIDE = 25344   # LDPC_HIP_HARQ_STRIDE
 
 
@@ -161,6 +163,17 @@ class ModDesc(ctypes.Structure):
 assert ctypes.sizeof(ModDesc) == 40
 
 
+class EqDesc(ctypes.Structure):
+    """ldpc_hip_eq_desc (include/srsran_ldpc_hip.h)."""
+    _fields_ = [("sym_offset", ctypes.c_uint64), ("sym_stride", ctypes.c_uint64), ("est_offset", ctypes.c_uint64),
+                ("est_stride", ctypes.c_uint64), ("out_offset", ctypes.c_uint64), ("nof_re", ctypes.c_uint32),
+                ("tx_scaling", ctypes.c_float), ("noise_var", ctypes.c_float * 4), ("algorithm", ctypes.c_uint8),
+                ("nof_rx_ports", ctypes.c_uint8), ("nof_tx_layers", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 5)]
+
+
+assert ctypes.sizeof(EqDesc) == 72
+
+
 class TbResult(ctypes.Structure):
     _fields_ = [("tb_crc_ok", ctypes.c_uint8), ("written", ctypes.c_uint8), ("nof_cbs_ok", ctypes.c_uint16)]
 
@@ -241,6 +254,9 @@ def load():
         "ldpc_hip_modulate_sync": (I, [P, U32, I, P, P, I]),
         "ldpc_hip_rate_match_modulate_launch": (I, [P, U32, ctypes.POINTER(RmDesc), ctypes.POINTER(ModDesc), P, P, I,
                                                     P]),
+        "ldpc_hip_equalize_supported": (I, [I, U32, U32]),
+        "ldpc_hip_equalize_launch": (I, [P, U32, ctypes.POINTER(EqDesc), P, P, P, P, P]),
+        "ldpc_hip_equalize_sync": (I, [P, I, U32, U32, U32, P, P, P, ctypes.c_float, P, P]),
         "ldpc_hip_capture_begin": (I, [P, P]),
         "ldpc_hip_capture_end": (I, [P, P, ctypes.POINTER(P)]),
         "ldpc_hip_graph_launch": (I, [P, P]),

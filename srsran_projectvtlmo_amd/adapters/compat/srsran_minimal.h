@@ -9,15 +9,18 @@
  *   srsran/hal/phy/upper/channel_processors/pusch/hw_accelerator_pusch_dec.h (+ _factory.h),
  *   srsran/hal/phy/upper/channel_processors/pusch/ext_harq_buffer_context_repository.h (+ _factory.h),
  *   srsran/hal/phy/upper/channel_processors/pusch/hw_accelerator_factories.h,
- *   srsran/hal/phy/upper/channel_processors/hw_accelerator_factories.h.
+ *   srsran/hal/phy/upper/channel_processors/hw_accelerator_factories.h,
+ *   srsran/adt/complex.h, srsran/adt/tensor.h, srsran/phy/upper/equalization/equalization_factories.h.
  * Only the members the adapters use are provided; names, layouts and semantics follow those headers.
  */
 #pragma once
 
+#include <array>
 #include <complex>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <optional>
 #include <string>
@@ -214,6 +217,140 @@ public:
   virtual std::unique_ptr<modulation_mapper>   create_modulation_mapper()   = 0;
   virtual std::unique_ptr<demodulation_mapper> create_demodulation_mapper() = 0;
   virtual std::unique_ptr<evm_calculator>      create_evm_calculator()      = 0;
+};
+
+/* bf16.h:35-72 and complex.h:50-63, 75-78: bfloat16 as its 16 bits (storage only), float to bf16 rounding to nearest
+ * with ties to even, bf16 to float by a 16-bit shift */
+struct bf16_t {
+  uint16_t bits = 0;
+  uint16_t value() const { return bits; }
+  bool     operator==(bf16_t o) const { return bits == o.bits; }
+  bool     operator!=(bf16_t o) const { return bits != o.bits; }
+};
+inline bf16_t to_bf16(float value)
+{
+  uint32_t u;
+  std::memcpy(&u, &value, sizeof(u));
+  u += 0x7fffU + ((u >> 16) & 1U);
+  return bf16_t{static_cast<uint16_t>(u >> 16)};
+}
+inline float to_float(bf16_t value)
+{
+  const uint32_t u = static_cast<uint32_t>(value.value()) << 16;
+  float          f;
+  std::memcpy(&f, &u, sizeof(f));
+  return f;
+}
+struct cbf16_t {
+  bf16_t real;
+  bf16_t imag;
+  cbf16_t(float real_ = 0.0F, float imag_ = 0.0F) : real(to_bf16(real_)), imag(to_bf16(imag_)) {}
+  cbf16_t(cf_t value) : cbf16_t(value.real(), value.imag()) {}
+  bool operator==(cbf16_t o) const { return real == o.real && imag == o.imag; }
+  bool operator!=(cbf16_t o) const { return !(*this == o); }
+};
+inline cf_t    to_cf(cbf16_t value) { return {to_float(value.real), to_float(value.imag)}; }
+inline cbf16_t to_cbf16(cf_t value) { return cbf16_t(value); }
+
+/* tensor.h:42-120, 228-285: an NDIMS-dimensional view of contiguous elements, dimension 0 the fastest, indexed by the
+ * enumerators of Index_type; dynamic_tensor owns its storage. Only what the equalizer and its callers use. */
+template <unsigned NDIMS, typename Type, typename Index_type = unsigned>
+class tensor
+{
+public:
+  using dims                 = Index_type;
+  using dimensions_size_type = std::array<unsigned, NDIMS>;
+  virtual ~tensor()          = default;
+  virtual const dimensions_size_type& get_dimensions_size() const                  = 0;
+  virtual void                        resize(const dimensions_size_type& dimensions) = 0;
+  virtual span<Type>                  get_data()                                   = 0;
+  virtual span<const Type>            get_data() const                             = 0;
+  unsigned get_dimension_size(Index_type i_dimension) const
+  {
+    return get_dimensions_size()[static_cast<unsigned>(i_dimension)];
+  }
+  /* the elements of the lowest N dimensions at the given indices of the others */
+  template <unsigned N = 1>
+  span<const Type> get_view(const std::array<unsigned, NDIMS - N>& indices) const
+  {
+    const dimensions_size_type& sz     = get_dimensions_size();
+    std::size_t                 stride = 1, offset = 0;
+    for (unsigned d = 0; d != N; ++d) {
+      stride *= sz[d];
+    }
+    const std::size_t view_size = stride;
+    for (unsigned d = N; d != NDIMS; ++d) {
+      srsran_assert(indices[d - N] < sz[d], "tensor index out of bounds");
+      offset += stride * indices[d - N];
+      stride *= sz[d];
+    }
+    return span<const Type>(get_data().data() + offset, view_size);
+  }
+  Type&       operator[](const dimensions_size_type& indices) { return get_data()[element_offset(indices)]; }
+  const Type& operator[](const dimensions_size_type& indices) const { return get_data()[element_offset(indices)]; }
+
+private:
+  std::size_t element_offset(const dimensions_size_type& indices) const
+  {
+    const dimensions_size_type& sz     = get_dimensions_size();
+    std::size_t                 stride = 1, offset = 0;
+    for (unsigned d = 0; d != NDIMS; ++d) {
+      srsran_assert(indices[d] < sz[d], "tensor index out of bounds");
+      offset += stride * indices[d];
+      stride *= sz[d];
+    }
+    return offset;
+  }
+};
+template <unsigned NDIMS, typename Type, typename Index_type = unsigned>
+class dynamic_tensor : public tensor<NDIMS, Type, Index_type>
+{
+public:
+  using dimensions_size_type = typename tensor<NDIMS, Type, Index_type>::dimensions_size_type;
+  dynamic_tensor()           = default;
+  explicit dynamic_tensor(const dimensions_size_type& dimensions) { resize(dimensions); }
+  const dimensions_size_type& get_dimensions_size() const override { return dimensions_size; }
+  void                        resize(const dimensions_size_type& dimensions) override
+  {
+    dimensions_size = dimensions;
+    std::size_t n   = 1;
+    for (unsigned d : dimensions) {
+      n *= d;
+    }
+    elements.resize(n);
+  }
+  span<Type>       get_data() override { return span<Type>(elements.data(), elements.size()); }
+  span<const Type> get_data() const override { return span<const Type>(elements.data(), elements.size()); }
+
+private:
+  dimensions_size_type dimensions_size = {};
+  std::vector<Type>    elements;
+};
+
+/* channel_equalizer_algorithm_type.h, channel_equalizer.h:37-102, equalization_factories.h:35-50 */
+enum class channel_equalizer_algorithm_type { zf = 0, mmse };
+class channel_equalizer
+{
+private:
+  enum class re_dims : unsigned { re = 0, slice = 1, nof_dims = 2 };
+  enum class ch_dims : unsigned { re = 0, rx_port = 1, tx_layer = 2, nof_dims = 3 };
+
+public:
+  using re_list              = tensor<2, cbf16_t, re_dims>;
+  using ch_est_list          = tensor<3, cbf16_t, ch_dims>;
+  virtual ~channel_equalizer() = default;
+  virtual void equalize(span<cf_t>         eq_symbols,
+                        span<float>        eq_noise_vars,
+                        const re_list&     ch_symbols,
+                        const ch_est_list& ch_estimates,
+                        span<const float>  noise_var_estimates,
+                        float              tx_scaling) = 0;
+};
+class channel_equalizer_factory
+{
+public:
+  virtual ~channel_equalizer_factory()                = default;
+  virtual std::unique_ptr<channel_equalizer> create() = 0;
 };
 
 namespace dpdk {

@@ -296,6 +296,58 @@ srsran::create_channel_modulation_factory_hip(int device, std::shared_ptr<channe
   return std::make_shared<channel_modulation_factory_hip>(device, std::move(evm_source));
 }
 
+/* ---- channel equalizer ---- */
+void channel_equalizer_hip::equalize(span<cf_t>         eq_symbols,
+                                     span<float>        eq_noise_vars,
+                                     const re_list&     ch_symbols,
+                                     const ch_est_list& ch_estimates,
+                                     span<const float>  noise_var_estimates,
+                                     float              tx_scaling)
+{
+  /* channel_equalizer_generic_impl.cpp:35-95, 175 (assert_sizes) */
+  const unsigned nof_re        = ch_symbols.get_dimension_size(re_list::dims::re);
+  const unsigned nof_rx_ports  = ch_estimates.get_dimension_size(ch_est_list::dims::rx_port);
+  const unsigned nof_tx_layers = ch_estimates.get_dimension_size(ch_est_list::dims::tx_layer);
+  srsran_assert(nof_re == ch_estimates.get_dimension_size(ch_est_list::dims::re),
+                "The number of channel estimates is not equal to the number of input RE.");
+  srsran_assert(eq_symbols.size() == eq_noise_vars.size(),
+                "The number of equalized RE is not equal to the number of noise variances.");
+  srsran_assert(nof_rx_ports == ch_symbols.get_dimension_size(re_list::dims::slice) &&
+                    nof_rx_ports == noise_var_estimates.size(),
+                "Number of Rx ports does not match.");
+  srsran_assert(static_cast<std::size_t>(nof_re) * nof_tx_layers == eq_symbols.size(),
+                "The number of channel estimates and layers is not consistent with the number of equalized RE.");
+  srsran_assert(tx_scaling > 0, "Tx scaling factor must be positive.");
+  srsran_assert(ldpc_hip_equalize_supported(static_cast<int>(type), nof_rx_ports, nof_tx_layers) == 1,
+                "Invalid combination of channel spatial topology and algorithm.");
+  static_assert(sizeof(cbf16_t) == 4 && sizeof(cf_t) == 8, "cbf16 is two bf16, cf_t two floats");
+  check_rc(ctx.get(),
+           ldpc_hip_equalize_sync(ctx.get(), static_cast<int>(type), nof_re, nof_rx_ports, nof_tx_layers,
+                                  reinterpret_cast<const uint16_t*>(ch_symbols.get_data().data()),
+                                  reinterpret_cast<const uint16_t*>(ch_estimates.get_data().data()),
+                                  noise_var_estimates.data(), tx_scaling, reinterpret_cast<float*>(eq_symbols.data()),
+                                  eq_noise_vars.data()));
+}
+
+namespace {
+class channel_equalizer_factory_hip : public channel_equalizer_factory
+{
+public:
+  channel_equalizer_factory_hip(channel_equalizer_algorithm_type type_, int dev) : type(type_), device(dev) {}
+  std::unique_ptr<channel_equalizer> create() override { return std::make_unique<channel_equalizer_hip>(type, device); }
+
+private:
+  channel_equalizer_algorithm_type type;
+  int                              device;
+};
+} // namespace
+
+std::shared_ptr<channel_equalizer_factory>
+srsran::create_channel_equalizer_factory_hip(channel_equalizer_algorithm_type type, int device)
+{
+  return std::make_shared<channel_equalizer_factory_hip>(type, device);
+}
+
 /* ---- HAL ---- */
 using namespace srsran::hal;
 

@@ -5,6 +5,7 @@
  *   srsran::ldpc_rate_dematcher_hip     : ldpc_rate_dematcher  (ldpc_rate_dematcher.h:35-56) factory type "hip"
  *   srsran::modulation_mapper_hip       : modulation_mapper    (modulation_mapper.h:35-64)    channel_modulation_factory
  *   srsran::demodulation_mapper_hip     : demodulation_mapper  (demodulation_mapper.h:46-70)  channel_modulation_factory
+ *   srsran::channel_equalizer_hip       : channel_equalizer    (channel_equalizer.h:37-102)   channel_equalizer_factory
  *   srsran::hal::hw_accelerator_pusch_dec_hip : hal::hw_accelerator_pusch_dec (hw_accelerator_pusch_dec.h:83-115)
  *                                                                                       acc_type "mi355x"
  *   srsran::hal::hw_accelerator_pdsch_enc_hip : hal::hw_accelerator_pdsch_enc (hw_accelerator_pdsch_enc.h:75-102)
@@ -27,6 +28,7 @@
 #include "srsran/hal/phy/upper/channel_processors/pusch/hw_accelerator_pusch_dec_factory.h"
 #include "srsran/phy/upper/channel_coding/channel_coding_factories.h"
 #include "srsran/phy/upper/channel_modulation/channel_modulation_factories.h"
+#include "srsran/phy/upper/equalization/equalization_factories.h"
 #include "srsran/support/srsran_assert.h"
 #else
 #include "compat/srsran_minimal.h"
@@ -159,6 +161,35 @@ private:
  * (e.g. create_channel_modulation_sw_factory()) when given, else nullptr. */
 std::shared_ptr<channel_modulation_factory>
 create_channel_modulation_factory_hip(int device = 0, std::shared_ptr<channel_modulation_factory> evm_source = nullptr);
+
+/* The channel equalizer on the GPU: the reference's scalar loops (equalize_zf_1xn.h, equalize_mmse_1xn.h,
+ * equalize_zf_2xn.h) bit for bit, through ldpc_hip_equalize_sync. ZF and MMSE with one layer on 1 to 4 receive ports,
+ * ZF with two layers on 2 or 4 ports; anything else asserts, as the reference does (its one-layer limit is 16 ports;
+ * 4 is the PUSCH processor's). */
+class channel_equalizer_hip : public channel_equalizer
+{
+public:
+  explicit channel_equalizer_hip(channel_equalizer_algorithm_type type_ = channel_equalizer_algorithm_type::zf,
+                                 int                              device = 0) :
+    type(type_), ctx(device)
+  {
+  }
+  void equalize(span<cf_t>         eq_symbols,
+                span<float>        eq_noise_vars,
+                const re_list&     ch_symbols,
+                const ch_est_list& ch_estimates,
+                span<const float>  noise_var_estimates,
+                float              tx_scaling) override;
+
+private:
+  channel_equalizer_algorithm_type type;
+  ldpc_hip_context                 ctx;
+};
+
+/* The factory create_channel_equalizer_generic_factory(type) stands for. */
+std::shared_ptr<channel_equalizer_factory>
+create_channel_equalizer_factory_hip(channel_equalizer_algorithm_type type = channel_equalizer_algorithm_type::zf,
+                                     int                              device = 0);
 
 namespace hal {
 

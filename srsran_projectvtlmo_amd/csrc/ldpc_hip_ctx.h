@@ -171,6 +171,8 @@ struct ldpc_hip_ctx {
   ldpc_hip::dev_buffer    d_modsegs; /* ldpc_hip_modulate_launch segments */
   ldpc_hip::dev_buffer    d_rmmod;   /* ldpc_hip_rate_match_modulate_launch codeblocks */
   ldpc_hip::desc_cache    c_modsegs, c_rmmod;
+  ldpc_hip::dev_buffer    d_eqsegs;  /* ldpc_hip_equalize_launch segments */
+  ldpc_hip::desc_cache    c_eqsegs;
   ldpc_hip::desc_cache    c_dmdesc, c_encdesc, c_rmdesc, c_dmsegs, c_tbaux; /* last uploads (upload_descs) */
   ldpc_hip::dev_buffer    d_tbaux;   /* ldpc_hip_tb_join_launch: its TB's descriptor, TB and chunk per workgroup */
   ldpc_hip::dev_buffer    d_tbwork;  /* ldpc_hip_tb_join_launch: per-TB chunk CRCs + arrival counter (zero at rest) */

@@ -1,0 +1,171 @@
+/*
+ * The channel equalizer's entry points of the C ABI (include/srsran_ldpc_hip.h): ldpc_hip_equalize_supported,
+ * ldpc_hip_equalize_launch and ldpc_hip_equalize_sync. The host validates the descriptors and counts the blocks; the
+ * kernel is ldpc_equalize_kernels.hip's.
+ */
+#include <vector>
+
+#include "ldpc_equalize.h"
+#include "ldpc_hip_ctx.h"
+
+using namespace ldpc_hip;
+
+namespace {
+
+constexpr uint64_t MAX_BLOCKS = 0x7fffffffULL;
+
+/* the work item of a descriptor; why != nullptr: refused */
+const char* make_eq_seg(const ldpc_hip_eq_desc& d, uint64_t& blocks, eq_seg& g)
+{
+  if (!eq_supported(d.algorithm, d.nof_rx_ports, d.nof_tx_layers)) {
+    return "equalize: unsupported (algorithm, rx ports, tx layers): ZF or MMSE with one layer on 1-4 ports, ZF with "
+           "two layers on 2 or 4 ports";
+  }
+  if (!(d.tx_scaling > 0.0F)) {
+    return "equalize: tx_scaling must be positive";
+  }
+  if (d.sym_stride < d.nof_re || d.est_stride < d.nof_re) {
+    return "equalize: a plane stride below nof_re";
+  }
+  if (static_cast<uint64_t>(d.nof_re) * d.nof_tx_layers >= 0x80000000ULL) {
+    /* a thread's first RE and its output index are 32-bit in the kernel, the last block's surplus threads included */
+    return "equalize: a segment holds fewer than 2^31 outputs";
+  }
+  g            = eq_seg{};
+  g.sym_offset = d.sym_offset;
+  g.sym_stride = d.sym_stride;
+  g.est_offset = d.est_offset;
+  g.est_stride = d.est_stride;
+  g.out_offset = d.out_offset;
+  g.nof_re     = d.nof_re;
+  g.block0     = static_cast<uint32_t>(blocks);
+  g.tx_scaling = d.tx_scaling;
+  for (uint32_t p = 0; p != EQ_MAX_PORTS; ++p) {
+    g.noise_var[p] = d.noise_var[p];
+  }
+  g.algorithm     = d.algorithm;
+  g.nof_rx_ports  = d.nof_rx_ports;
+  g.nof_tx_layers = d.nof_tx_layers;
+  constexpr uint64_t per_block = static_cast<uint64_t>(EQ_BLOCK) * EQ_RES;
+  blocks += (d.nof_re + per_block - 1U) / per_block;
+  return blocks > MAX_BLOCKS ? "equalize: too many REs for one launch" : nullptr;
+}
+
+int equalize_segments(ldpc_hip_ctx* ctx, uint32_t nof_segs, const ldpc_hip_eq_desc* descs, const uint16_t* d_sym,
+                      const uint16_t* d_est, float* d_eq, float* d_nv, hipStream_t s)
+{
+  std::vector<eq_seg> sg;
+  sg.reserve(nof_segs);
+  uint64_t blocks = 0;
+  for (uint32_t i = 0; i != nof_segs; ++i) {
+    eq_seg         g;
+    const uint64_t before = blocks;
+    if (const char* why = make_eq_seg(descs[i], blocks, g)) {
+      return ctx->fail(LDPC_HIP_EINVAL, why);
+    }
+    if (blocks != before) {
+      sg.push_back(g);
+    }
+  }
+  if (sg.empty()) {
+    return LDPC_HIP_OK;
+  }
+  hipError_t e = upload_descs(ctx->d_eqsegs, ctx->c_eqsegs, sg.data(), sg.size() * sizeof(eq_seg), s);
+  if (e == hipSuccess) {
+    e = launch_equalize(ctx->d_eqsegs.as<eq_seg>(), static_cast<uint32_t>(sg.size()), static_cast<uint32_t>(blocks),
+                        d_sym, d_est, d_eq, d_nv, s);
+  }
+  return e == hipSuccess ? LDPC_HIP_OK : ctx->hip_fail(e, "ldpc_equalize_kernel launch");
+}
+
+} // namespace
+
+extern "C" {
+
+int ldpc_hip_equalize_supported(int algorithm, uint32_t nof_rx_ports, uint32_t nof_tx_layers)
+{
+  return eq_supported(algorithm, nof_rx_ports, nof_tx_layers) ? 1 : 0;
+}
+
+int ldpc_hip_equalize_launch(ldpc_hip_ctx* ctx, uint32_t nof_segs, const ldpc_hip_eq_desc* descs,
+                             const uint16_t* d_ch_symbols, const uint16_t* d_ch_estimates, float* d_eq_symbols,
+                             float* d_eq_noise_vars, void* stream)
+{
+  if (ctx == nullptr) {
+    return LDPC_HIP_EINVAL;
+  }
+  if (nof_segs == 0) {
+    return LDPC_HIP_OK;
+  }
+  if (descs == nullptr || d_ch_symbols == nullptr || d_ch_estimates == nullptr || d_eq_symbols == nullptr ||
+      d_eq_noise_vars == nullptr) {
+    return ctx->fail(LDPC_HIP_EINVAL, "equalize_launch: null argument");
+  }
+  (void)hipSetDevice(ctx->device);
+  return equalize_segments(ctx, nof_segs, descs, d_ch_symbols, d_ch_estimates, d_eq_symbols, d_eq_noise_vars,
+                           abi_stream(ctx->stream, stream));
+}
+
+int ldpc_hip_equalize_sync(ldpc_hip_ctx* ctx, int algorithm, uint32_t nof_re, uint32_t nof_rx_ports,
+                           uint32_t nof_tx_layers, const uint16_t* ch_symbols, const uint16_t* ch_estimates,
+                           const float* noise_vars, float tx_scaling, float* eq_symbols, float* eq_noise_vars)
+{
+  if (ctx == nullptr) {
+    return LDPC_HIP_EINVAL;
+  }
+  ldpc_hip_eq_desc d{};
+  d.sym_stride = d.est_stride = d.nof_re = nof_re;
+  d.tx_scaling                           = tx_scaling;
+  uint64_t blocks = 0;
+  eq_seg   g;
+  if (eq_supported(algorithm, nof_rx_ports, nof_tx_layers)) {
+    d.algorithm     = static_cast<uint8_t>(algorithm);
+    d.nof_rx_ports  = static_cast<uint8_t>(nof_rx_ports);
+    d.nof_tx_layers = static_cast<uint8_t>(nof_tx_layers);
+  } else {
+    d.algorithm = 0xffU; /* refused below with the launch's message */
+  }
+  if (const char* why = make_eq_seg(d, blocks, g)) {
+    return ctx->fail(LDPC_HIP_EINVAL, why);
+  }
+  if (nof_re == 0) {
+    return LDPC_HIP_OK;
+  }
+  if (ch_symbols == nullptr || ch_estimates == nullptr || noise_vars == nullptr || eq_symbols == nullptr ||
+      eq_noise_vars == nullptr) {
+    return ctx->fail(LDPC_HIP_EINVAL, "equalize_sync: null argument");
+  }
+  for (uint32_t p = 0; p != nof_rx_ports; ++p) {
+    d.noise_var[p] = noise_vars[p];
+  }
+  (void)hipSetDevice(ctx->device);
+  const size_t nsym = static_cast<size_t>(nof_re) * nof_rx_ports * 4U;
+  const size_t nest = nsym * nof_tx_layers;
+  const size_t nout = static_cast<size_t>(nof_re) * nof_tx_layers;
+  hipError_t   e;
+  /* d_llr: received REs then estimates (nsym is a multiple of 4 bytes, so the estimates stay element-aligned) */
+  if ((e = ctx->d_llr.reserve(nsym + nest)) != hipSuccess || (e = ctx->d_sym.reserve(nout * 8U)) != hipSuccess ||
+      (e = ctx->d_nv.reserve(nout * 4U)) != hipSuccess) {
+    return ctx->hip_fail(e, "hipMalloc(equalize)");
+  }
+  uint8_t* in = ctx->d_llr.as<uint8_t>();
+  if ((e = hipMemcpyAsync(in, ch_symbols, nsym, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(in + nsym, ch_estimates, nest, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) {
+    return ctx->hip_fail(e, "hipMemcpyAsync(equalize in)");
+  }
+  const int r = equalize_segments(ctx, 1, &d, reinterpret_cast<const uint16_t*>(in),
+                                  reinterpret_cast<const uint16_t*>(in + nsym), ctx->d_sym.as<float>(),
+                                  ctx->d_nv.as<float>(), ctx->stream);
+  if (r != LDPC_HIP_OK) {
+    return r;
+  }
+  if ((e = hipMemcpyAsync(eq_symbols, ctx->d_sym.ptr, nout * 8U, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(eq_noise_vars, ctx->d_nv.ptr, nout * 4U, hipMemcpyDeviceToHost, ctx->stream)) !=
+          hipSuccess ||
+      (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
+    return ctx->hip_fail(e, "equalize_sync");
+  }
+  return LDPC_HIP_OK;
+}
+
+} /* extern "C" */

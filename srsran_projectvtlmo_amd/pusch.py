@@ -210,6 +210,8 @@ class SlotPipeline:
         self.d_sym = None          # complex symbols (float re, im) and noise variances, allocated by upload_symbols
         self.d_nv = None
         self.from_symbols = False
+        self.from_channel = False  # upload_channel: launch() equalises into d_sym / d_nv first
+        self._eq_key = None        # the staged equalizer segments (shapes, algorithms, scalings, variances)
         self._graph = None         # ldpc_hip_graph of capture()
         # from symbols: demodulation fused into the dematcher when every CB's E fits its LDS staging
         self.fuse_demod = all(d.rm_length <= 32768 for d in dm)
@@ -235,6 +237,69 @@ class SlotPipeline:
         self.d_sym = torch.from_numpy(h_sym.view(np.float32)).to(dev)
         self.d_nv = torch.from_numpy(h_nv).to(dev)
         self.from_symbols = True
+        self.from_channel = False
+
+    def upload_channel(self, ch_symbols_per_tb, ch_estimates_per_tb, noise_vars_per_tb, algorithm=0,
+                       tx_scaling=1.0) -> None:
+        """Stage the slot's received REs and channel estimates instead of equalised symbols: ch_symbols_per_tb[i] is
+        TB i's cbf16 REs (uint16 [port, re, 2]), ch_estimates_per_tb[i] its estimates (uint16 [layer, port, re, 2]) and
+        noise_vars_per_tb[i] one noise variance per port, as pusch_demodulator_impl hands them to
+        channel_equalizer::equalize (pusch_demodulator_impl.cpp:221-243); nof_re x layers must equal the TB's symbol
+        count. algorithm (equalization.channel_equalizer_algorithm_type) and tx_scaling: one value, or one per TB.
+        launch() then runs one ldpc_hip_equalize_launch into the symbols and noise variances of the from-symbols path.
+        The device buffers stay where they are from one upload to the next of the same shapes, so a captured graph
+        reads the new REs; an upload that changes a shape, an algorithm, a scaling or a variance changes the
+        equalizer's descriptors and drops the captured graph (capture() again)."""
+        import torch
+
+        from . import equalization
+        np = self._np
+        n_tb = len(self.tbs)
+        algs = list(algorithm) if isinstance(algorithm, (list, tuple)) else [algorithm] * n_tb
+        scs = list(tx_scaling) if isinstance(tx_scaling, (list, tuple)) else [tx_scaling] * n_tb
+        if not (len(ch_symbols_per_tb) == len(ch_estimates_per_tb) == len(noise_vars_per_tb) == len(algs) ==
+                len(scs) == n_tb):
+            raise ValueError("one entry per TB")
+        segs, syms, ests = [], [], []
+        so = eo = 0
+        for o, tb, y, h, nv, alg, sc in zip(self.tb_symbol_offsets, self.tbs, ch_symbols_per_tb, ch_estimates_per_tb,
+                                            noise_vars_per_tb, algs, scs):
+            y, h = np.ascontiguousarray(y), np.ascontiguousarray(h)
+            if y.dtype != np.uint16 or h.dtype != np.uint16 or y.ndim != 3 or h.ndim != 4 or y.shape[-1] != 2 or \
+                    h.shape[-1] != 2 or h.shape[1:3] != y.shape[:2] or len(nv) != y.shape[0]:
+                raise ValueError("cbf16 REs are uint16 [port, re, 2], estimates uint16 [layer, port, re, 2], one "
+                                 "noise variance per port")
+            L, P, n = h.shape[:3]
+            cnt = sum(tb.rm_lengths) // tb.modulation_order
+            if n * L != cnt:
+                raise ValueError(f"TB needs nof_re x layers == {cnt} symbols")
+            if not equalization.equalize_supported(alg, P, L):
+                raise ValueError(f"no equalizer for algorithm {int(alg)}, {P} ports, {L} layers")
+            segs.append(equalization.eq_segment(n, P, L, [float(v) for v in nv], int(alg), float(sc), so, eo, o))
+            syms.append(y.reshape(-1, 2))
+            ests.append(h.reshape(-1, 2))
+            so += (P * n + 3) // 4 * 4          # every TB's planes start on a 16-byte boundary
+            eo += (L * P * n + 3) // 4 * 4
+        h_sym, h_est = np.zeros((max(4, so), 2), np.uint16), np.zeros((max(4, eo), 2), np.uint16)
+        for s, y, h in zip(segs, syms, ests):
+            h_sym[s.sym_offset:s.sym_offset + len(y)] = y
+            h_est[s.est_offset:s.est_offset + len(h)] = h
+        key = [(s.nof_re, s.nof_rx_ports, s.nof_tx_layers, tuple(s.noise_vars), s.algorithm, s.tx_scaling)
+               for s in segs]
+        dev = torch.device("cuda", self.ctx.device)
+        if key != self._eq_key or not self.from_channel:
+            self.release_graph()
+            self._eq_key, self._eq_n = key, len(segs)
+            self._eq_arr = equalization.eq_descriptors(segs)
+            self.d_ch_sym = torch.zeros(h_sym.shape, dtype=torch.int16, device=dev)   # cbf16 bit patterns
+            self.d_ch_est = torch.zeros(h_est.shape, dtype=torch.int16, device=dev)
+            self.d_sym = torch.zeros(2 * max(1, self.nof_symbols), dtype=torch.float32, device=dev)
+            self.d_nv = torch.zeros(max(1, self.nof_symbols), dtype=torch.float32, device=dev)
+        # blocking copies (pageable memory), as upload(): the launch may go to another stream
+        self.d_ch_sym.copy_(torch.from_numpy(h_sym.view(np.int16)))
+        self.d_ch_est.copy_(torch.from_numpy(h_est.view(np.int16)))
+        torch.cuda.current_stream().synchronize()
+        self.from_symbols = self.from_channel = True
 
     def upload_symbols_device(self, symbols_per_tb, noise_vars_per_tb) -> None:
         """As upload_symbols(), from device tensors (complex64 symbols, float32 noise variances per TB)."""
@@ -249,6 +314,7 @@ class SlotPipeline:
             self.d_sym[2 * o:2 * (o + cnt)].copy_(torch.view_as_real(z.reshape(-1)).reshape(-1))
             self.d_nv[o:o + cnt].copy_(n.reshape(-1))
         self.from_symbols = True
+        self.from_channel = False
 
     def upload(self, llrs_per_tb, stream=None) -> None:
         """llrs_per_tb[i][r]: int8 E-LLRs of CB r of TB i (host arrays); those of a TB with rnti >= 0 are still
@@ -275,6 +341,11 @@ class SlotPipeline:
         336-346); new-data TBs decode every CB."""
         L, c = self.ctx.lib, self.ctx.handle
         from . import channel_modulation, sequence_generators
+        if self.from_channel:
+            # received REs and estimates to the symbols and noise variances the from-symbols path reads
+            from . import equalization
+            equalization.equalize_launch(self.ctx, self._eq_arr, self.d_ch_sym.data_ptr(), self.d_ch_est.data_ptr(),
+                                         self.d_sym.data_ptr(), self.d_nv.data_ptr(), stream, n=self._eq_n)
         sym = self.from_symbols and self.fuse_demod           # symbols demodulated inside the dematcher
         scr, llr_off = None, self._llr_off
         if self.from_symbols and not self.fuse_demod:

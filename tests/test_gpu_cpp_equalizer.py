@@ -1,0 +1,19 @@
+"""Runs the C++ equalizer test program (tests/cpp/test_equalizer.cpp): equalizers made by
+create_channel_equalizer_factory_hip equalise all ten topologies against the scalar rule the program carries."""
+import subprocess
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+ADAPTERS = ROOT / "srsran_projectvtlmo_amd" / "adapters"
+PROGRAM = ROOT / "tests" / "cpp" / "build" / "test_equalizer"
+
+
+@pytest.mark.gpu
+def test_cpp_equalizer_all_topologies():
+    subprocess.run(["make", "-s", "-C", str(ADAPTERS), "test-equalizer"], check=True)
+    r = subprocess.run([str(PROGRAM)], capture_output=True, text=True, timeout=120)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "PASS" in r.stdout
