@@ -153,14 +153,14 @@ void ldpc_hip_harq_repo::release()
 
 namespace ldpc_hip {
 
-hipError_t upload_descs(dev_buffer& buf, desc_cache& last, const void* src, size_t n, hipStream_t s)
+hipError_t desc_table::upload(const void* src, size_t n, hipStream_t s)
 {
   hipError_t e = buf.reserve(n);
   if (e != hipSuccess) {
     return e;
   }
   const auto* b = static_cast<const uint8_t*>(src);
-  if (last.ptr == buf.ptr && last.stream == s && last.bytes.size() == n && std::memcmp(last.bytes.data(), b, n) == 0) {
+  if (last_ptr == buf.ptr && last_stream == s && last.size() == n && std::memcmp(last.data(), b, n) == 0) {
     return hipSuccess;
   }
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -169,11 +169,11 @@ hipError_t upload_descs(dev_buffer& buf, desc_cache& last, const void* src, size
   }
   e = hipMemcpyAsync(buf.ptr, src, n, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) {
-    last.bytes.assign(b, b + n);
-    last.ptr    = buf.ptr;
-    last.stream = s;
+    last.assign(b, b + n);
+    last_ptr    = buf.ptr;
+    last_stream = s;
   } else {
-    last = desc_cache{};
+    last_ptr = nullptr; /* forgotten: no buffer's address */
   }
   return e;
 }
@@ -362,36 +362,13 @@ int demodulate_segments(ldpc_hip_ctx* ctx, uint32_t nof_segs, const ldpc_hip_dem
                         const float* d_nv, int8_t* d_llr, hipStream_t s)
 {
   std::vector<demod_seg> sg;
-  sg.reserve(nof_segs);
-  uint32_t blocks = 0;
-  for (uint32_t i = 0; i != nof_segs; ++i) {
-    const ldpc_hip_demod_desc& d = descs[i];
-    if (!valid_modulation(d.modulation)) {
-      return ctx->fail(LDPC_HIP_EINVAL, "demodulate: invalid modulation scheme");
-    }
-    if (d.nof_symbols == 0) {
-      continue;
-    }
-    demod_seg g{};
-    g.sym_offset   = d.symbol_offset;
-    g.noise_offset = d.noise_offset;
-    g.llr_offset   = d.llr_offset;
-    g.nof_symbols  = d.nof_symbols;
-    g.block0       = blocks;
-    g.modulation   = d.modulation;
-    g.qm           = static_cast<uint8_t>(bits_per_symbol(d.modulation));
-    sg.push_back(g);
-    blocks += (d.nof_symbols + DEMOD_BLOCK - 1) / DEMOD_BLOCK;
+  uint32_t               blocks = 0;
+  if (const char* why = make_segs(nof_segs, descs, sg, blocks, make_demod_seg)) {
+    return ctx->fail(LDPC_HIP_EINVAL, why);
   }
-  if (sg.empty()) {
-    return LDPC_HIP_OK;
-  }
-  hipError_t e = upload_descs(ctx->d_dmsegs, ctx->c_dmsegs, sg.data(), sg.size() * sizeof(demod_seg), s);
-  if (e == hipSuccess) {
-    e = launch_demodulate(ctx->d_dmsegs.as<demod_seg>(), static_cast<uint32_t>(sg.size()), blocks, ctx->dtab, d_sym,
-                          d_nv, d_llr, s);
-  }
-  return e == hipSuccess ? LDPC_HIP_OK : ctx->hip_fail(e, "ldpc_demodulate_kernel launch");
+  return ctx->launch_items(ctx->d_dmsegs, sg, s, "ldpc_demodulate_kernel launch", [&](const demod_seg* d_segs) {
+    return launch_demodulate(d_segs, static_cast<uint32_t>(sg.size()), blocks, ctx->dtab, d_sym, d_nv, d_llr, s);
+  });
 }
 
 /* ---- pseudo-random sequences: descrambling and the packed-bit scrambler ----
@@ -400,40 +377,13 @@ int prs_segments(ldpc_hip_ctx* ctx, uint32_t nof_segs, const ldpc_hip_prs_seg* s
                  uint8_t* d_out, hipStream_t s)
 {
   std::vector<prs_seg> sg;
-  sg.reserve(nof_segs);
-  uint64_t blocks = 0;
-  for (uint32_t i = 0; i != nof_segs; ++i) {
-    const ldpc_hip_prs_seg& d = segs[i];
-    if ((d.c_init & ~PRS_MASK) != 0U) {
-      return ctx->fail(LDPC_HIP_EINVAL, "pseudo-random sequence: c_init above 31 bits");
-    }
-    if (d.length == 0) {
-      continue;
-    }
-    const ldpc_hip_prs_state st = prs_state_at(d.c_init, d.seq_offset);
-    prs_seg                  g{};
-    g.in_offset  = d_in != nullptr ? d.in_offset : PRS_NO_INPUT;
-    g.out_offset = d.out_offset;
-    g.length     = d.length;
-    g.block0     = static_cast<uint32_t>(blocks);
-    g.x1         = st.x1;
-    g.x2         = st.x2;
-    sg.push_back(g);
-    const uint64_t words = (static_cast<uint64_t>(d.length) + 31U) / 32U;
-    blocks += (words + PRS_BLOCK * PRS_WORDS - 1U) / (PRS_BLOCK * PRS_WORDS);
-    if (blocks > 0x7fffffffULL) {
-      return ctx->fail(LDPC_HIP_EINVAL, "pseudo-random sequence: too many LLRs or bits for one launch");
-    }
+  uint32_t             blocks = 0;
+  if (const char* why = make_segs(nof_segs, segs, sg, blocks, make_prs_seg, d_in != nullptr)) {
+    return ctx->fail(LDPC_HIP_EINVAL, why);
   }
-  if (sg.empty()) {
-    return LDPC_HIP_OK;
-  }
-  hipError_t e = upload_descs(ctx->d_prssegs, ctx->c_prssegs, sg.data(), sg.size() * sizeof(prs_seg), s);
-  if (e == hipSuccess) {
-    e = launch_prs(ctx->d_prssegs.as<prs_seg>(), static_cast<uint32_t>(sg.size()), static_cast<uint32_t>(blocks), bits,
-                   d_in, d_out, s);
-  }
-  return e == hipSuccess ? LDPC_HIP_OK : ctx->hip_fail(e, "ldpc_prs_kernel launch");
+  return ctx->launch_items(ctx->d_prssegs, sg, s, "ldpc_prs_kernel launch", [&](const prs_seg* d_segs) {
+    return launch_prs(d_segs, static_cast<uint32_t>(sg.size()), blocks, bits, d_in, d_out, s);
+  });
 }
 
 } // namespace ldpc_hip
@@ -966,13 +916,10 @@ int ldpc_hip_rate_dematch_scr_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const 
   }
   (void)hipSetDevice(ctx->device);
   hipStream_t s = abi_stream(ctx->stream, stream);
-  hipError_t  e = upload_descs(ctx->d_dmdesc, ctx->c_dmdesc, dm.data(), nof_cbs * sizeof(dematch_cb), s);
-  if (e == hipSuccess) {
-    e = launch_dematch(ctx->d_dmdesc.as<dematch_cb>(), nof_cbs, ctx->dtab, s);
-  }
-  return e == hipSuccess ? LDPC_HIP_OK
-                         : ctx->hip_fail(e, demod != nullptr ? "ldpc_rate_dematch_kernel launch (demodulating)"
-                                                             : "ldpc_rate_dematch_kernel launch");
+  return ctx->launch_items(ctx->d_dmdesc, dm, s,
+                           demod != nullptr ? "ldpc_rate_dematch_kernel launch (demodulating)"
+                                            : "ldpc_rate_dematch_kernel launch",
+                           [&](const dematch_cb* d_cbs) { return launch_dematch(d_cbs, nof_cbs, ctx->dtab, s); });
 }
 
 int ldpc_hip_rate_dematch_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldpc_hip_dematch_desc* descs,
@@ -1049,7 +996,7 @@ int ldpc_hip_dematch_decode_scr_launch(ldpc_hip_plan* plan, const ldpc_hip_demat
   (void)hipSetDevice(ctx->device);
   const uint32_t   dm_lds = dm_fused_budget(dm.data(), dm.size());
   hipStream_t      hs = abi_stream(ctx->stream, stream);
-  const hipError_t e  = upload_descs(plan->d_dm, plan->c_dm, dm.data(), dm.size() * sizeof(dematch_cb), hs);
+  const hipError_t e  = plan->d_dm.upload(dm.data(), dm.size() * sizeof(dematch_cb), hs);
   if (e != hipSuccess) {
     return ctx->hip_fail(e, "dematch_decode_launch: descriptors");
   }
@@ -1076,12 +1023,10 @@ int ldpc_hip_encode_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldpc_hip_e
     }
   }
   (void)hipSetDevice(ctx->device);
-  hipStream_t s  = abi_stream(ctx->stream, stream);
-  hipError_t  er = upload_descs(ctx->d_encdesc, ctx->c_encdesc, e.data(), nof_cbs * sizeof(enc_cb), s);
-  if (er == hipSuccess) {
-    er = launch_encode(ctx->d_encdesc.as<enc_cb>(), nof_cbs, d_msgs, d_cws, ctx->d_crc.as<uint32_t>(), s);
-  }
-  return er == hipSuccess ? LDPC_HIP_OK : ctx->hip_fail(er, "ldpc_encode_kernel launch");
+  hipStream_t s = abi_stream(ctx->stream, stream);
+  return ctx->launch_items(ctx->d_encdesc, e, s, "ldpc_encode_kernel launch", [&](const enc_cb* d_cbs) {
+    return launch_encode(d_cbs, nof_cbs, d_msgs, d_cws, ctx->d_crc.as<uint32_t>(), s);
+  });
 }
 
 int ldpc_hip_rate_match_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldpc_hip_rm_desc* descs,
@@ -1104,12 +1049,10 @@ int ldpc_hip_rate_match_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldpc_h
     }
   }
   (void)hipSetDevice(ctx->device);
-  hipStream_t s  = abi_stream(ctx->stream, stream);
-  hipError_t  er = upload_descs(ctx->d_rmdesc, ctx->c_rmdesc, r.data(), nof_cbs * sizeof(ratematch_cb), s);
-  if (er == hipSuccess) {
-    er = launch_rate_match(ctx->d_rmdesc.as<ratematch_cb>(), nof_cbs, d_cws, d_out, s);
-  }
-  return er == hipSuccess ? LDPC_HIP_OK : ctx->hip_fail(er, "ldpc_rate_match_kernel launch");
+  hipStream_t s = abi_stream(ctx->stream, stream);
+  return ctx->launch_items(ctx->d_rmdesc, r, s, "ldpc_rate_match_kernel launch", [&](const ratematch_cb* d_cbs) {
+    return launch_rate_match(d_cbs, nof_cbs, d_cws, d_out, s);
+  });
 }
 
 int ldpc_hip_tb_join_launch(ldpc_hip_ctx* ctx, uint32_t nof_tbs, const ldpc_hip_tb_desc* descs, const uint8_t* d_msgs,
@@ -1140,7 +1083,7 @@ int ldpc_hip_tb_join_launch(ldpc_hip_ctx* ctx, uint32_t nof_tbs, const ldpc_hip_
     }
   }
   const uint32_t nblocks = static_cast<uint32_t>(blocks.size());
-  hipError_t     e       = upload_descs(ctx->d_tbaux, ctx->c_tbaux, blocks.data(), nblocks * sizeof(tbj_block), s);
+  hipError_t     e       = ctx->d_tbaux.upload(blocks.data(), nblocks * sizeof(tbj_block), s);
   const size_t work_bytes = static_cast<size_t>(nof_tbs) * TBJ_WORK_WORDS * 4;
   if (e == hipSuccess && ctx->d_tbwork.size < work_bytes) {
     /* arrival counters start at zero; the kernel returns each to zero after its TB */

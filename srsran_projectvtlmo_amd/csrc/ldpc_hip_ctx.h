@@ -2,7 +2,8 @@
  * The host runtime's shared state behind the C ABI of include/srsran_ldpc_hip.h: the context, decode plans, the HAL
  * queue's operations and the external HARQ repository, with the functions its units call across each other:
  * ldpc_hip_api.cpp (context, plans, *_launch entry points), ldpc_hip_sync.cpp (synchronous entry points),
- * ldpc_hip_hal.cpp (HAL decoder queue) and ldpc_hip_enc_queue.cpp (PDSCH encoder queue).
+ * ldpc_hip_modulate.cpp (modulation mapper), ldpc_hip_equalize.cpp (channel equalizer), ldpc_hip_hal.cpp (HAL decoder
+ * queue), ldpc_hip_enc_queue.cpp (PDSCH encoder queue) and ldpc_hip_descs.cpp (descriptor translations, host only).
  */
 #pragma once
 
@@ -119,15 +120,20 @@ struct ldpc_hip_harq_repo {
 
 namespace ldpc_hip {
 
-/* Descriptor upload of the *_launch entry points. A slot pipeline relaunches the same descriptors slot after slot,
- * and a host-to-device copy from pageable memory is performed synchronously by HIP (the host waits for the stream),
- * so an upload equal to the previous one into the same buffer, on the same stream, is skipped. */
-struct desc_cache {
-  std::vector<uint8_t> bytes;
-  void*                ptr    = nullptr;
-  hipStream_t          stream = nullptr;
+/* The device copy of a *_launch entry point's work items, with what was last uploaded into it. A slot pipeline
+ * relaunches the same descriptors slot after slot, and a host-to-device copy from pageable memory is performed
+ * synchronously by HIP (the host waits for the stream), so an upload equal to the previous one into the same
+ * allocation, on the same stream, is skipped; any other is refused while the stream is capturing. */
+struct desc_table {
+  hipError_t upload(const void* src, size_t n, hipStream_t s);
+  template <typename T>
+  const T* as() const { return buf.as<const T>(); }
+private:
+  dev_buffer           buf;
+  std::vector<uint8_t> last; /* the bytes in buf[0, last.size()), copied there on last_stream at address last_ptr */
+  void*                last_ptr    = nullptr;
+  hipStream_t          last_stream = nullptr;
 };
-hipError_t upload_descs(dev_buffer& buf, desc_cache& last, const void* src, size_t n, hipStream_t s);
 
 /* The HIP stream an entry point's `stream` argument names: NULL the context's own stream; hipStreamLegacy
  * ((hipStream_t)1, the legacy default stream) the null stream, which is that stream to every runtime call; any other
@@ -162,19 +168,16 @@ struct ldpc_hip_ctx {
   std::vector<uint8_t>    graph_spec; /* id + 1 of the specialised kernel (ldpc_spec.h) for this graph, 0: none */
   ldpc_hip::dev_buffer    d_crc;
   ldpc_hip::dev_buffer    d_tasks; /* step_task records of all graphs (ldpc_graph.cpp build_tasks) */
-  ldpc_hip::dev_buffer    d_dmdesc; /* ldpc_hip_rate_dematch_launch descriptors */
-  ldpc_hip::dev_buffer    d_encdesc; /* ldpc_hip_encode_launch descriptors */
-  ldpc_hip::dev_buffer    d_rmdesc;  /* ldpc_hip_rate_match_launch descriptors */
-  ldpc_hip::dev_buffer    d_dmsegs;  /* ldpc_hip_demodulate_launch segments */
-  ldpc_hip::dev_buffer    d_prssegs; /* ldpc_hip_descramble_launch / ldpc_hip_scramble_bits_launch segments */
-  ldpc_hip::desc_cache    c_prssegs;
-  ldpc_hip::dev_buffer    d_modsegs; /* ldpc_hip_modulate_launch segments */
-  ldpc_hip::dev_buffer    d_rmmod;   /* ldpc_hip_rate_match_modulate_launch codeblocks */
-  ldpc_hip::desc_cache    c_modsegs, c_rmmod;
-  ldpc_hip::dev_buffer    d_eqsegs;  /* ldpc_hip_equalize_launch segments */
-  ldpc_hip::desc_cache    c_eqsegs;
-  ldpc_hip::desc_cache    c_dmdesc, c_encdesc, c_rmdesc, c_dmsegs, c_tbaux; /* last uploads (upload_descs) */
-  ldpc_hip::dev_buffer    d_tbaux;   /* ldpc_hip_tb_join_launch: its TB's descriptor, TB and chunk per workgroup */
+  /* the *_launch entry points' work items on the device (launch_items) */
+  ldpc_hip::desc_table    d_dmdesc;  /* ldpc_hip_rate_dematch_launch descriptors */
+  ldpc_hip::desc_table    d_encdesc; /* ldpc_hip_encode_launch descriptors */
+  ldpc_hip::desc_table    d_rmdesc;  /* ldpc_hip_rate_match_launch descriptors */
+  ldpc_hip::desc_table    d_dmsegs;  /* ldpc_hip_demodulate_launch segments */
+  ldpc_hip::desc_table    d_prssegs; /* ldpc_hip_descramble_launch / ldpc_hip_scramble_bits_launch segments */
+  ldpc_hip::desc_table    d_modsegs; /* ldpc_hip_modulate_launch segments */
+  ldpc_hip::desc_table    d_rmmod;   /* ldpc_hip_rate_match_modulate_launch codeblocks */
+  ldpc_hip::desc_table    d_eqsegs;  /* ldpc_hip_equalize_launch segments */
+  ldpc_hip::desc_table    d_tbaux;   /* ldpc_hip_tb_join_launch: its TB's descriptor, TB and chunk per workgroup */
   ldpc_hip::dev_buffer    d_tbwork;  /* ldpc_hip_tb_join_launch: per-TB chunk CRCs + arrival counter (zero at rest) */
   ldpc_hip::demod_tables  dtab{};    /* demodulator slopes / intercepts (make_demod_tables) */
   ldpc_hip_params         params{};
@@ -238,6 +241,21 @@ struct ldpc_hip_ctx {
     err = where + ": " + hipGetErrorString(e);
     return LDPC_HIP_EDEVICE;
   }
+  /* The tail of a *_launch entry point: the work items into their table on stream s, then launch(the device items);
+   * a HIP error of either is reported as `what`. No item (every segment empty): nothing touches the device. */
+  template <typename T, typename Launch>
+  int launch_items(ldpc_hip::desc_table& table, const std::vector<T>& items, hipStream_t s, const char* what,
+                   Launch&& launch)
+  {
+    if (items.empty()) {
+      return LDPC_HIP_OK;
+    }
+    hipError_t e = table.upload(items.data(), items.size() * sizeof(T), s);
+    if (e == hipSuccess) {
+      e = launch(table.as<T>());
+    }
+    return e == hipSuccess ? LDPC_HIP_OK : hip_fail(e, what);
+  }
 };
 
 struct launch_group {
@@ -267,8 +285,7 @@ struct ldpc_hip_plan {
   /* the device descriptors in block order on the host (block i decodes caller descriptor h_cbs[i].result_index), and
    * the fused dematcher's descriptors in the same order (ldpc_hip_dematch_decode_launch) */
   std::vector<ldpc_hip::dec_cb> h_cbs;
-  ldpc_hip::dev_buffer          d_dm;
-  ldpc_hip::desc_cache          c_dm;
+  ldpc_hip::desc_table          d_dm;
 };
 
 namespace ldpc_hip {

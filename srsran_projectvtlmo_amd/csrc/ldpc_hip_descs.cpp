@@ -51,6 +51,13 @@ uint32_t prs_advance(uint32_t s, uint64_t n)
 unsigned bg_K(int bg) { return bg == 1 ? 22U : 10U; }
 unsigned bg_N_full(int bg) { return bg == 1 ? 68U : 52U; }
 
+/* a segment's blocks onto its launch's count; more than one launch holds: `too_many` */
+const char* add_blocks(uint64_t& blocks, uint64_t units, uint64_t per_block, const char* too_many)
+{
+  blocks += (units + per_block - 1U) / per_block;
+  return blocks <= MAX_LAUNCH_BLOCKS ? nullptr : too_many;
+}
+
 } // namespace
 
 /* Nc = 1600 bits on from the initial registers, then offset (two jumps: 1600 + offset may not fit 64 bits) */
@@ -306,6 +313,122 @@ const char* make_pdsch_cb(const ldpc_hip_enc_desc& ed, const uint32_t* ext, cons
     why = "pdsch_encode: encoder and rate matcher descriptors disagree";
   }
   return why;
+}
+
+/* ---- segment launches ---- */
+const char* make_demod_seg(const ldpc_hip_demod_desc& d, uint64_t& blocks, demod_seg& out)
+{
+  if (!valid_modulation(d.modulation)) {
+    return "demodulate: invalid modulation scheme";
+  }
+  out              = demod_seg{};
+  out.sym_offset   = d.symbol_offset;
+  out.noise_offset = d.noise_offset;
+  out.llr_offset   = d.llr_offset;
+  out.nof_symbols  = d.nof_symbols;
+  out.block0       = static_cast<uint32_t>(blocks);
+  out.modulation   = d.modulation;
+  out.qm           = static_cast<uint8_t>(bits_per_symbol(d.modulation));
+  return add_blocks(blocks, d.nof_symbols, DEMOD_BLOCK, "demodulate: too many symbols for one launch");
+}
+
+const char* make_prs_seg(const ldpc_hip_prs_seg& d, uint64_t& blocks, prs_seg& out, bool has_input)
+{
+  if ((d.c_init & ~PRS_MASK) != 0U) {
+    return "pseudo-random sequence: c_init above 31 bits";
+  }
+  const ldpc_hip_prs_state st = prs_state_at(d.c_init, d.seq_offset);
+  out                         = prs_seg{};
+  out.in_offset               = has_input ? d.in_offset : PRS_NO_INPUT;
+  out.out_offset              = d.out_offset;
+  out.length                  = d.length;
+  out.block0                  = static_cast<uint32_t>(blocks);
+  out.x1                      = st.x1;
+  out.x2                      = st.x2;
+  return add_blocks(blocks, (static_cast<uint64_t>(d.length) + 31U) / 32U, PRS_BLOCK * PRS_WORDS,
+                    "pseudo-random sequence: too many LLRs or bits for one launch");
+}
+
+const char* make_mod_seg(const ldpc_hip_mod_desc& d, uint64_t& blocks, mod_seg& out)
+{
+  if (!valid_modulation(d.modulation)) {
+    return "modulate: invalid modulation scheme";
+  }
+  if (d.scramble != 0 && (d.c_init & ~PRS_MASK) != 0U) {
+    return "modulate: c_init above 31 bits";
+  }
+  if (d.nof_symbols >= 0x80000000U) {
+    /* a thread's first symbol (chunk x symbols per chunk) is 32-bit in the kernels, the last block's surplus threads
+     * included */
+    return "modulate: a segment holds fewer than 2^31 symbols";
+  }
+  const uint32_t qm = bits_per_symbol(d.modulation);
+  out               = mod_seg{};
+  out.bit_offset    = d.bit_offset;
+  out.sym_offset    = d.symbol_offset;
+  out.nof_symbols   = d.nof_symbols;
+  out.block0        = static_cast<uint32_t>(blocks);
+  out.modulation    = d.modulation;
+  if (d.scramble != 0) {
+    const ldpc_hip_prs_state st = prs_state_at(d.c_init, d.seq_offset);
+    out.x1                      = st.x1;
+    out.x2                      = st.x2;
+  }
+  const uint64_t per_chunk = mod_chunk_bits(qm) / qm;
+  return add_blocks(blocks, (d.nof_symbols + per_chunk - 1U) / per_chunk, MOD_BLOCK,
+                    "modulate: too many symbols for one launch");
+}
+
+const char* make_rm_mod_cb(const ldpc_hip_rm_desc& rd, const ldpc_hip_mod_desc& md, uint64_t& blocks, rm_mod_cb& out)
+{
+  const char* why = make_rm_cb(rd, out.rm);
+  if (why == nullptr) {
+    why = make_mod_seg(md, blocks, out.mod);
+  }
+  if (why == nullptr && md.modulation == LDPC_HIP_MOD_PI_2_BPSK) {
+    why = "rate_match_modulate_launch: pi/2-BPSK is not a PDSCH scheme (a span per codeblock would restart the "
+          "symbol parity): rate-match, then ldpc_hip_modulate_launch over the codeword";
+  }
+  if (why == nullptr && (bits_per_symbol(md.modulation) != rd.modulation_order ||
+                         static_cast<uint64_t>(md.nof_symbols) * rd.modulation_order != rd.rm_length ||
+                         rd.rm_length >= 0x80000000U)) {
+    why = "rate_match_modulate_launch: symbols x bits per symbol must equal rm_length, the scheme's bits per symbol "
+          "modulation_order";
+  }
+  return why;
+}
+
+const char* make_eq_seg(const ldpc_hip_eq_desc& d, uint64_t& blocks, eq_seg& out)
+{
+  if (!eq_supported(d.algorithm, d.nof_rx_ports, d.nof_tx_layers)) {
+    return "equalize: unsupported (algorithm, rx ports, tx layers): ZF or MMSE with one layer on 1-4 ports, ZF with "
+           "two layers on 2 or 4 ports";
+  }
+  if (!(d.tx_scaling > 0.0F)) {
+    return "equalize: tx_scaling must be positive";
+  }
+  if (d.sym_stride < d.nof_re || d.est_stride < d.nof_re) {
+    return "equalize: a plane stride below nof_re";
+  }
+  if (static_cast<uint64_t>(d.nof_re) * d.nof_tx_layers >= 0x80000000ULL) {
+    /* a thread's first RE and its output index are 32-bit in the kernel, the last block's surplus threads included */
+    return "equalize: a segment holds fewer than 2^31 outputs";
+  }
+  out            = eq_seg{};
+  out.sym_offset = d.sym_offset;
+  out.sym_stride = d.sym_stride;
+  out.est_offset = d.est_offset;
+  out.est_stride = d.est_stride;
+  out.out_offset = d.out_offset;
+  out.nof_re     = d.nof_re;
+  out.block0     = static_cast<uint32_t>(blocks);
+  out.tx_scaling = d.tx_scaling;
+  std::copy(d.noise_var, d.noise_var + EQ_MAX_PORTS, out.noise_var);
+  out.algorithm     = d.algorithm;
+  out.nof_rx_ports  = d.nof_rx_ports;
+  out.nof_tx_layers = d.nof_tx_layers;
+  return add_blocks(blocks, d.nof_re, static_cast<uint64_t>(EQ_BLOCK) * EQ_RES,
+                    "equalize: too many REs for one launch");
 }
 
 } // namespace ldpc_hip

@@ -1,14 +1,15 @@
 /*
  * The one translation of each C-ABI descriptor (include/srsran_ldpc_hip.h) into the work item the kernels read
- * (ldpc_hip_device.h), with its validation. Host only: no HIP runtime call, no context. Each make_* returns the reason
- * its descriptor is invalid, or nullptr after filling the work item; the entry points report the reason through
- * ldpc_hip_last_error with LDPC_HIP_EINVAL.
+ * (ldpc_hip_device.h, ldpc_equalize.h), with its validation, the segment launches' included. Host only: no HIP runtime
+ * call, no context. Each make_* returns the reason its descriptor is invalid, or nullptr after filling the work item;
+ * the entry points report the reason through ldpc_hip_last_error with LDPC_HIP_EINVAL.
  */
 #pragma once
 
 #include <cstdint>
 #include <vector>
 
+#include "ldpc_equalize.h"
 #include "ldpc_graph.h"
 
 namespace ldpc_hip {
@@ -58,5 +59,37 @@ const char* make_enc_cb(const ldpc_hip_enc_desc& d, const uint32_t* ext, enc_cb&
 const char* make_rm_cb(const ldpc_hip_rm_desc& d, ratematch_cb& out);
 const char* make_pdsch_cb(const ldpc_hip_enc_desc& ed, const uint32_t* ext, const ldpc_hip_rm_desc& rd,
                           pdsch_enc_cb& out);
+
+/* ---- segment launches: demodulator, pseudo-random sequences (has_input false, the scrambler generating: in_offset
+ * is PRS_NO_INPUT), modulation mapper, equalizer ---- An item's block0 is `blocks`, its launch's count so far, which
+ * the translation advances by the segment's blocks and refuses above MAX_LAUNCH_BLOCKS (a grid's 32-bit x). */
+constexpr uint64_t MAX_LAUNCH_BLOCKS = 0x7fffffffULL;
+const char* make_demod_seg(const ldpc_hip_demod_desc& d, uint64_t& blocks, demod_seg& out);
+const char* make_prs_seg(const ldpc_hip_prs_seg& d, uint64_t& blocks, prs_seg& out, bool has_input);
+const char* make_mod_seg(const ldpc_hip_mod_desc& d, uint64_t& blocks, mod_seg& out);
+const char* make_eq_seg(const ldpc_hip_eq_desc& d, uint64_t& blocks, eq_seg& out);
+/* the fused launch's codeblock: make_rm_cb, make_mod_seg, then that the pair agrees */
+const char* make_rm_mod_cb(const ldpc_hip_rm_desc& rd, const ldpc_hip_mod_desc& md, uint64_t& blocks, rm_mod_cb& out);
+/* A launch's segments through make(descriptor, blocks, item, more...): every descriptor validated in the caller's
+ * order, a segment that takes no block (zero length) then dropped; nblocks is the launch's grid. */
+template <typename D, typename G, typename Make, typename... More>
+const char* make_segs(uint32_t n, const D* descs, std::vector<G>& segs, uint32_t& nblocks, Make make, More... more)
+{
+  segs.clear();
+  segs.reserve(n);
+  uint64_t blocks = 0;
+  for (uint32_t i = 0; i != n; ++i) {
+    G              g;
+    const uint64_t before = blocks;
+    if (const char* why = make(descs[i], blocks, g, more...)) {
+      return why;
+    }
+    if (blocks != before) {
+      segs.push_back(g);
+    }
+  }
+  nblocks = static_cast<uint32_t>(blocks);
+  return nullptr;
+}
 
 } // namespace ldpc_hip

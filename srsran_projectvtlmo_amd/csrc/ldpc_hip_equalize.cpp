@@ -1,81 +1,27 @@
 /*
  * The channel equalizer's entry points of the C ABI (include/srsran_ldpc_hip.h): ldpc_hip_equalize_supported,
- * ldpc_hip_equalize_launch and ldpc_hip_equalize_sync. The host validates the descriptors and counts the blocks; the
- * kernel is ldpc_equalize_kernels.hip's.
+ * ldpc_hip_equalize_launch and ldpc_hip_equalize_sync. The descriptors become work items in ldpc_hip_descs.cpp
+ * (validation and the block count); the kernel is ldpc_equalize_kernels.hip's.
  */
 #include <vector>
 
-#include "ldpc_equalize.h"
 #include "ldpc_hip_ctx.h"
 
 using namespace ldpc_hip;
 
 namespace {
 
-constexpr uint64_t MAX_BLOCKS = 0x7fffffffULL;
-
-/* the work item of a descriptor; why != nullptr: refused */
-const char* make_eq_seg(const ldpc_hip_eq_desc& d, uint64_t& blocks, eq_seg& g)
-{
-  if (!eq_supported(d.algorithm, d.nof_rx_ports, d.nof_tx_layers)) {
-    return "equalize: unsupported (algorithm, rx ports, tx layers): ZF or MMSE with one layer on 1-4 ports, ZF with "
-           "two layers on 2 or 4 ports";
-  }
-  if (!(d.tx_scaling > 0.0F)) {
-    return "equalize: tx_scaling must be positive";
-  }
-  if (d.sym_stride < d.nof_re || d.est_stride < d.nof_re) {
-    return "equalize: a plane stride below nof_re";
-  }
-  if (static_cast<uint64_t>(d.nof_re) * d.nof_tx_layers >= 0x80000000ULL) {
-    /* a thread's first RE and its output index are 32-bit in the kernel, the last block's surplus threads included */
-    return "equalize: a segment holds fewer than 2^31 outputs";
-  }
-  g            = eq_seg{};
-  g.sym_offset = d.sym_offset;
-  g.sym_stride = d.sym_stride;
-  g.est_offset = d.est_offset;
-  g.est_stride = d.est_stride;
-  g.out_offset = d.out_offset;
-  g.nof_re     = d.nof_re;
-  g.block0     = static_cast<uint32_t>(blocks);
-  g.tx_scaling = d.tx_scaling;
-  for (uint32_t p = 0; p != EQ_MAX_PORTS; ++p) {
-    g.noise_var[p] = d.noise_var[p];
-  }
-  g.algorithm     = d.algorithm;
-  g.nof_rx_ports  = d.nof_rx_ports;
-  g.nof_tx_layers = d.nof_tx_layers;
-  constexpr uint64_t per_block = static_cast<uint64_t>(EQ_BLOCK) * EQ_RES;
-  blocks += (d.nof_re + per_block - 1U) / per_block;
-  return blocks > MAX_BLOCKS ? "equalize: too many REs for one launch" : nullptr;
-}
-
 int equalize_segments(ldpc_hip_ctx* ctx, uint32_t nof_segs, const ldpc_hip_eq_desc* descs, const uint16_t* d_sym,
                       const uint16_t* d_est, float* d_eq, float* d_nv, hipStream_t s)
 {
   std::vector<eq_seg> sg;
-  sg.reserve(nof_segs);
-  uint64_t blocks = 0;
-  for (uint32_t i = 0; i != nof_segs; ++i) {
-    eq_seg         g;
-    const uint64_t before = blocks;
-    if (const char* why = make_eq_seg(descs[i], blocks, g)) {
-      return ctx->fail(LDPC_HIP_EINVAL, why);
-    }
-    if (blocks != before) {
-      sg.push_back(g);
-    }
+  uint32_t            blocks = 0;
+  if (const char* why = make_segs(nof_segs, descs, sg, blocks, make_eq_seg)) {
+    return ctx->fail(LDPC_HIP_EINVAL, why);
   }
-  if (sg.empty()) {
-    return LDPC_HIP_OK;
-  }
-  hipError_t e = upload_descs(ctx->d_eqsegs, ctx->c_eqsegs, sg.data(), sg.size() * sizeof(eq_seg), s);
-  if (e == hipSuccess) {
-    e = launch_equalize(ctx->d_eqsegs.as<eq_seg>(), static_cast<uint32_t>(sg.size()), static_cast<uint32_t>(blocks),
-                        d_sym, d_est, d_eq, d_nv, s);
-  }
-  return e == hipSuccess ? LDPC_HIP_OK : ctx->hip_fail(e, "ldpc_equalize_kernel launch");
+  return ctx->launch_items(ctx->d_eqsegs, sg, s, "ldpc_equalize_kernel launch", [&](const eq_seg* d_segs) {
+    return launch_equalize(d_segs, static_cast<uint32_t>(sg.size()), blocks, d_sym, d_est, d_eq, d_nv, s);
+  });
 }
 
 } // namespace

@@ -1,53 +1,18 @@
 /*
  * The modulation mapper's entry points of the C ABI (include/srsran_ldpc_hip.h): ldpc_hip_modulation_scaling,
- * ldpc_hip_modulate_launch / _sync and ldpc_hip_rate_match_modulate_launch. The host validates the descriptors,
- * computes one generator start state per scrambled segment (prs_state_at) and counts the blocks; the kernels are
+ * ldpc_hip_modulate_launch / _sync and ldpc_hip_rate_match_modulate_launch. The descriptors become work items in
+ * ldpc_hip_descs.cpp (validation, one generator start state per scrambled segment, the block count); the kernels are
  * ldpc_modulation_kernels.hip's.
  */
 #include <cstring>
 #include <vector>
 
 #include "ldpc_hip_ctx.h"
-#include "ldpc_hip_descs.h"
 #include "ldpc_hip_launch.h"
 
 using namespace ldpc_hip;
 
 namespace {
-
-constexpr uint64_t MAX_BLOCKS = 0x7fffffffULL;
-
-/* the mapper's part of a work item; why != nullptr: refused */
-const char* make_mod_seg(const ldpc_hip_mod_desc& d, uint64_t& blocks, mod_seg& g)
-{
-  if (!valid_modulation(d.modulation)) {
-    return "modulate: invalid modulation scheme";
-  }
-  if (d.scramble != 0 && (d.c_init & ~PRS_MASK) != 0U) {
-    return "modulate: c_init above 31 bits";
-  }
-  if (d.nof_symbols >= 0x80000000U) {
-    /* a thread's first symbol (chunk x symbols per chunk) is 32-bit in the kernels, the last block's surplus threads
-     * included */
-    return "modulate: a segment holds fewer than 2^31 symbols";
-  }
-  const uint32_t qm = bits_per_symbol(d.modulation);
-  g                 = mod_seg{};
-  g.bit_offset      = d.bit_offset;
-  g.sym_offset      = d.symbol_offset;
-  g.nof_symbols     = d.nof_symbols;
-  g.block0          = static_cast<uint32_t>(blocks);
-  g.modulation      = d.modulation;
-  if (d.scramble != 0) {
-    const ldpc_hip_prs_state st = prs_state_at(d.c_init, d.seq_offset);
-    g.x1                        = st.x1;
-    g.x2                        = st.x2;
-  }
-  const uint64_t per_chunk = mod_chunk_bits(qm) / qm;
-  const uint64_t chunks    = (d.nof_symbols + per_chunk - 1U) / per_chunk;
-  blocks += (chunks + MOD_BLOCK - 1U) / MOD_BLOCK;
-  return blocks > MAX_BLOCKS ? "modulate: too many symbols for one launch" : nullptr;
-}
 
 bool valid_format(int format) { return format == LDPC_HIP_SYM_CF32 || format == LDPC_HIP_SYM_CI8; }
 
@@ -55,27 +20,14 @@ int modulate_segments(ldpc_hip_ctx* ctx, uint32_t nof_segs, const ldpc_hip_mod_d
                       void* d_symbols, int format, hipStream_t s)
 {
   std::vector<mod_seg> sg;
-  sg.reserve(nof_segs);
-  uint64_t blocks = 0;
-  for (uint32_t i = 0; i != nof_segs; ++i) {
-    mod_seg        g;
-    const uint64_t before = blocks;
-    if (const char* why = make_mod_seg(descs[i], blocks, g)) {
-      return ctx->fail(LDPC_HIP_EINVAL, why);
-    }
-    if (blocks != before) {
-      sg.push_back(g);
-    }
+  uint32_t             blocks = 0;
+  if (const char* why = make_segs(nof_segs, descs, sg, blocks, make_mod_seg)) {
+    return ctx->fail(LDPC_HIP_EINVAL, why);
   }
-  if (sg.empty()) {
-    return LDPC_HIP_OK;
-  }
-  hipError_t e = upload_descs(ctx->d_modsegs, ctx->c_modsegs, sg.data(), sg.size() * sizeof(mod_seg), s);
-  if (e == hipSuccess) {
-    e = launch_modulate(ctx->d_modsegs.as<mod_seg>(), static_cast<uint32_t>(sg.size()), static_cast<uint32_t>(blocks),
-                        format == LDPC_HIP_SYM_CI8, d_bits, d_symbols, s);
-  }
-  return e == hipSuccess ? LDPC_HIP_OK : ctx->hip_fail(e, "ldpc_modulate_kernel launch");
+  return ctx->launch_items(ctx->d_modsegs, sg, s, "ldpc_modulate_kernel launch", [&](const mod_seg* d_segs) {
+    return launch_modulate(d_segs, static_cast<uint32_t>(sg.size()), blocks, format == LDPC_HIP_SYM_CI8, d_bits,
+                           d_symbols, s);
+  });
 }
 
 } // namespace
@@ -170,32 +122,17 @@ int ldpc_hip_rate_match_modulate_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, con
   std::vector<rm_mod_cb> cbs(nof_cbs);
   uint64_t               blocks = 0;
   for (uint32_t i = 0; i != nof_cbs; ++i) {
-    const char* why = make_rm_cb(descs[i], cbs[i].rm);
-    if (why == nullptr) {
-      why = make_mod_seg(mod[i], blocks, cbs[i].mod);
-    }
-    if (why == nullptr && mod[i].modulation == LDPC_HIP_MOD_PI_2_BPSK) {
-      why = "rate_match_modulate_launch: pi/2-BPSK is not a PDSCH scheme (a span per codeblock would restart the "
-            "symbol parity): rate-match, then ldpc_hip_modulate_launch over the codeword";
-    }
-    if (why == nullptr && (bits_per_symbol(mod[i].modulation) != descs[i].modulation_order ||
-                           static_cast<uint64_t>(mod[i].nof_symbols) * descs[i].modulation_order != descs[i].rm_length ||
-                           descs[i].rm_length >= 0x80000000U)) {
-      why = "rate_match_modulate_launch: symbols x bits per symbol must equal rm_length, the scheme's bits per symbol "
-            "modulation_order";
-    }
-    if (why != nullptr) {
+    if (const char* why = make_rm_mod_cb(descs[i], mod[i], blocks, cbs[i])) {
       return ctx->fail(LDPC_HIP_EINVAL, why);
     }
   }
   (void)hipSetDevice(ctx->device);
   hipStream_t s = abi_stream(ctx->stream, stream);
-  hipError_t  e = upload_descs(ctx->d_rmmod, ctx->c_rmmod, cbs.data(), cbs.size() * sizeof(rm_mod_cb), s);
-  if (e == hipSuccess) {
-    e = launch_rate_match_modulate(ctx->d_rmmod.as<rm_mod_cb>(), nof_cbs, static_cast<uint32_t>(blocks),
-                                   format == LDPC_HIP_SYM_CI8, d_cws, d_symbols, s);
-  }
-  return e == hipSuccess ? LDPC_HIP_OK : ctx->hip_fail(e, "ldpc_rate_match_modulate_kernel launch");
+  return ctx->launch_items(ctx->d_rmmod, cbs, s, "ldpc_rate_match_modulate_kernel launch",
+                           [&](const rm_mod_cb* d_cbs) {
+                             return launch_rate_match_modulate(d_cbs, nof_cbs, static_cast<uint32_t>(blocks),
+                                                               format == LDPC_HIP_SYM_CI8, d_cws, d_symbols, s);
+                           });
 }
 
 } /* extern "C" */

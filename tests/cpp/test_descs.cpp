@@ -2,6 +2,7 @@
  * descriptors, one rejection per reason, the order of the checks, and the one-CB / plan equivalence. Links the
  * host-only units alone (no HIP runtime); built with AddressSanitizer and UBSan by tests/test_descs_host.py.
  * The expected reasons are the texts of the entry points' errors before the translations were gathered in one unit. */
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -48,6 +49,27 @@ static const char* const R_DM_DEMOD   = "demod_dematch_launch: symbols x bits pe
 static const char* const R_DM_DEMOD_F = "dematch_decode_launch: symbols x bits per symbol must equal rm_length <= 32768";
 static const char* const R_DM_SCR     = "scrambled codeblock with rm_length above 32768 cannot be descrambled in the "
                                         "dematcher: descramble it with ldpc_hip_descramble_launch first";
+
+static const char* const R_DEMOD_MOD   = "demodulate: invalid modulation scheme";
+static const char* const R_DEMOD_MANY  = "demodulate: too many symbols for one launch";
+static const char* const R_PRS_CINIT   = "pseudo-random sequence: c_init above 31 bits";
+static const char* const R_PRS_MANY    = "pseudo-random sequence: too many LLRs or bits for one launch";
+static const char* const R_MOD_MOD     = "modulate: invalid modulation scheme";
+static const char* const R_MOD_CINIT   = "modulate: c_init above 31 bits";
+static const char* const R_MOD_SEG     = "modulate: a segment holds fewer than 2^31 symbols";
+static const char* const R_MOD_MANY    = "modulate: too many symbols for one launch";
+static const char* const R_RMMOD_BPSK  = "rate_match_modulate_launch: pi/2-BPSK is not a PDSCH scheme (a span per "
+                                         "codeblock would restart the symbol parity): rate-match, then "
+                                         "ldpc_hip_modulate_launch over the codeword";
+static const char* const R_RMMOD_PAIR  = "rate_match_modulate_launch: symbols x bits per symbol must equal rm_length, "
+                                         "the scheme's bits per symbol modulation_order";
+static const char* const R_RM_PARAMS   = "rate_match_launch: invalid parameters";
+static const char* const R_EQ_TOPOLOGY = "equalize: unsupported (algorithm, rx ports, tx layers): ZF or MMSE with one "
+                                         "layer on 1-4 ports, ZF with two layers on 2 or 4 ports";
+static const char* const R_EQ_SCALING  = "equalize: tx_scaling must be positive";
+static const char* const R_EQ_STRIDE   = "equalize: a plane stride below nof_re";
+static const char* const R_EQ_SEG      = "equalize: a segment holds fewer than 2^31 outputs";
+static const char* const R_EQ_MANY     = "equalize: too many REs for one launch";
 
 static ldpc_hip_dec_desc dec_desc(int bg, unsigned Z)
 {
@@ -472,6 +494,257 @@ static void test_tb_join()
   REASON(tb_desc_reason(d), "tb_join: invalid sizes");
 }
 
+/* the segment launches' array forms, as their entry points call them */
+static const char* make_demod_segs(uint32_t n, const ldpc_hip_demod_desc* d, std::vector<demod_seg>& g, uint32_t& nb)
+{
+  return make_segs(n, d, g, nb, make_demod_seg);
+}
+static const char* make_prs_segs(uint32_t n, const ldpc_hip_prs_seg* d, bool has_input, std::vector<prs_seg>& g,
+                                 uint32_t& nb)
+{
+  return make_segs(n, d, g, nb, make_prs_seg, has_input);
+}
+static const char* make_mod_segs(uint32_t n, const ldpc_hip_mod_desc* d, std::vector<mod_seg>& g, uint32_t& nb)
+{
+  return make_segs(n, d, g, nb, make_mod_seg);
+}
+static const char* make_eq_segs(uint32_t n, const ldpc_hip_eq_desc* d, std::vector<eq_seg>& g, uint32_t& nb)
+{
+  return make_segs(n, d, g, nb, make_eq_seg);
+}
+
+/* `count` copies of d hold at most MAX_LAUNCH_BLOCKS blocks, each per_seg of them, and one more does not */
+template <typename D, typename G, typename Make>
+static void check_block_cap(const D& d, uint32_t count, uint32_t per_seg, const char* reason, Make make)
+{
+  CHECK(static_cast<uint64_t>(count) * per_seg <= MAX_LAUNCH_BLOCKS);
+  CHECK(static_cast<uint64_t>(count + 1) * per_seg > MAX_LAUNCH_BLOCKS);
+  std::vector<D> descs(count + 1, d);
+  std::vector<G> segs;
+  uint32_t       nblocks = 0;
+  CHECK(make(count, descs.data(), segs, nblocks) == nullptr && segs.size() == count && nblocks == count * per_seg);
+  CHECK(segs[count - 1].block0 == (count - 1) * per_seg);
+  REASON(make(count + 1, descs.data(), segs, nblocks), reason);
+}
+
+static void test_demodulator()
+{
+  ldpc_hip_demod_desc d[3]{};
+  d[0].symbol_offset = 5, d[0].noise_offset = 7, d[0].llr_offset = 128, d[0].nof_symbols = 64, d[0].modulation = 2;
+  d[1].modulation    = 4; /* empty: validated, then dropped */
+  d[2].symbol_offset = 69, d[2].noise_offset = 71, d[2].llr_offset = 256, d[2].nof_symbols = 300, d[2].modulation = 6;
+  std::vector<demod_seg> sg;
+  uint32_t               nblocks = 0;
+  CHECK(make_demod_segs(3, d, sg, nblocks) == nullptr && sg.size() == 2 && nblocks == 3);
+  CHECK(sg[0].sym_offset == 5 && sg[0].noise_offset == 7 && sg[0].llr_offset == 128 && sg[0].nof_symbols == 64);
+  CHECK(sg[0].block0 == 0 && sg[0].modulation == 2 && sg[0].qm == 2);
+  CHECK(sg[1].sym_offset == 69 && sg[1].noise_offset == 71 && sg[1].llr_offset == 256 && sg[1].nof_symbols == 300);
+  CHECK(sg[1].block0 == 1 && sg[1].modulation == 6 && sg[1].qm == 6);
+  for (const demod_seg& g : sg) {
+    for (const uint8_t p : g.pad) {
+      CHECK(p == 0);
+    }
+  }
+  /* pi/2-BPSK: one bit per symbol; a whole block and one symbol more */
+  d[0].modulation = 0, d[0].nof_symbols = 257;
+  CHECK(make_demod_segs(1, d, sg, nblocks) == nullptr && sg.size() == 1 && sg[0].qm == 1 && nblocks == 2);
+  CHECK(make_demod_segs(0, nullptr, sg, nblocks) == nullptr && sg.empty() && nblocks == 0);
+  d[1].modulation = 3; /* the empty segment's scheme counts */
+  REASON(make_demod_segs(3, d, sg, nblocks), R_DEMOD_MOD);
+  ldpc_hip_demod_desc big{};
+  big.nof_symbols = 0xffffffffU; /* 2^24 blocks */
+  big.modulation  = 2;
+  check_block_cap<ldpc_hip_demod_desc, demod_seg>(big, 127, 1U << 24, R_DEMOD_MANY, make_demod_segs);
+}
+
+static void test_sequences()
+{
+  ldpc_hip_prs_seg s[3]{};
+  s[0].in_offset = 5, s[0].out_offset = 7, s[0].seq_offset = 12345, s[0].length = 1, s[0].c_init = 0x1234567U;
+  s[1].in_offset = 9, s[1].c_init = 3; /* empty */
+  s[2].in_offset = 64, s[2].out_offset = 96, s[2].seq_offset = 31, s[2].length = 32769, s[2].c_init = 0x7fffffffU;
+  for (const bool has_input : {true, false}) {
+    std::vector<prs_seg> sg;
+    uint32_t             nblocks = 0;
+    CHECK(make_prs_segs(3, s, has_input, sg, nblocks) == nullptr && sg.size() == 2);
+    /* 1 bit is one word, one block; 32769 bits are 1025 words, one more than a block's PRS_BLOCK x PRS_WORDS */
+    CHECK(nblocks == 3 && sg[0].block0 == 0 && sg[1].block0 == 1);
+    CHECK(sg[0].in_offset == (has_input ? 5U : PRS_NO_INPUT) && sg[1].in_offset == (has_input ? 64U : PRS_NO_INPUT));
+    CHECK(sg[0].out_offset == 7 && sg[0].length == 1 && sg[1].out_offset == 96 && sg[1].length == 32769);
+    const ldpc_hip_prs_state r0 = prs_reference(0x1234567U, 12345), r1 = prs_reference(0x7fffffffU, 31);
+    CHECK(sg[0].x1 == r0.x1 && sg[0].x2 == r0.x2 && sg[1].x1 == r1.x1 && sg[1].x2 == r1.x2);
+  }
+  std::vector<prs_seg> sg;
+  uint32_t             nblocks = 0;
+  s[1].c_init = 0x80000000U; /* the empty segment's c_init counts */
+  REASON(make_prs_segs(3, s, true, sg, nblocks), R_PRS_CINIT);
+  ldpc_hip_prs_seg big{};
+  big.length = 0xffffffffU; /* 2^27 words, 2^17 blocks */
+  check_block_cap<ldpc_hip_prs_seg, prs_seg>(
+      big, 16383, 1U << 17, R_PRS_MANY,
+      [](uint32_t n, const ldpc_hip_prs_seg* d, std::vector<prs_seg>& g, uint32_t& b) {
+        return make_prs_segs(n, d, false, g, b);
+      });
+}
+
+static ldpc_hip_mod_desc mod_desc(unsigned modulation, uint32_t nof_symbols, bool scramble)
+{
+  ldpc_hip_mod_desc d{};
+  d.bit_offset    = 11;
+  d.symbol_offset = 13;
+  d.seq_offset    = 777;
+  d.nof_symbols   = nof_symbols;
+  d.c_init        = scramble ? 0x2345678U : 0xffffffffU; /* ignored when the bits are mapped as they are */
+  d.modulation    = static_cast<uint8_t>(modulation);
+  d.scramble      = scramble ? 1 : 0;
+  return d;
+}
+
+static void test_mapper()
+{
+  /* a thread maps one chunk of 32 bits (96 for 64-QAM), a block MOD_BLOCK chunks: 100 QPSK symbols are 7 chunks, 4097
+   * symbols of 64-QAM 257 chunks, 1025 symbols of 256-QAM 257 chunks */
+  const ldpc_hip_mod_desc d[4] = {mod_desc(2, 100, true), mod_desc(4, 0, true), mod_desc(6, 4097, false),
+                                  mod_desc(8, 1025, true)};
+  std::vector<mod_seg>    sg;
+  uint32_t                nblocks = 0;
+  CHECK(make_mod_segs(4, d, sg, nblocks) == nullptr && sg.size() == 3 && nblocks == 5);
+  const uint32_t           block0[3] = {0, 1, 3}, syms[3] = {100, 4097, 1025}, mods[3] = {2, 6, 8};
+  const ldpc_hip_prs_state ref       = prs_reference(0x2345678U, 777);
+  for (int i = 0; i != 3; ++i) {
+    CHECK(sg[i].bit_offset == 11 && sg[i].sym_offset == 13 && sg[i].nof_symbols == syms[i]);
+    CHECK(sg[i].block0 == block0[i] && sg[i].modulation == mods[i]);
+    CHECK(sg[i].x1 == (i == 1 ? 0U : ref.x1) && sg[i].x2 == (i == 1 ? 0U : ref.x2));
+    for (const uint8_t p : sg[i].pad) {
+      CHECK(p == 0);
+    }
+  }
+  /* one descriptor: the item starts at the launch's count so far and advances it */
+  uint64_t blocks = 40;
+  mod_seg  g;
+  CHECK(make_mod_seg(d[2], blocks, g) == nullptr && g.block0 == 40 && blocks == 42);
+  CHECK(make_mod_seg(d[1], blocks, g) == nullptr && blocks == 42);
+  ldpc_hip_mod_desc x = mod_desc(3, 100, true);
+  REASON(make_mod_seg(x, blocks, g), R_MOD_MOD);
+  x = mod_desc(2, 100, true), x.c_init = 0x80000000U;
+  REASON(make_mod_seg(x, blocks, g), R_MOD_CINIT);
+  x = mod_desc(2, 0x80000000U, true);
+  REASON(make_mod_seg(x, blocks, g), R_MOD_SEG);
+  /* order: scheme, c_init, the segment's size */
+  x.c_init = 0x80000000U;
+  REASON(make_mod_seg(x, blocks, g), R_MOD_CINIT);
+  x.modulation = 5;
+  REASON(make_mod_seg(x, blocks, g), R_MOD_MOD);
+  REASON(make_mod_segs(1, &x, sg, nblocks), R_MOD_MOD);
+  /* 2^31 - 1 symbols of 256-QAM: 2^29 chunks, 2^21 blocks */
+  check_block_cap<ldpc_hip_mod_desc, mod_seg>(mod_desc(8, 0x7fffffffU, false), 1023, 1U << 21, R_MOD_MANY,
+                                              make_mod_segs);
+}
+
+static void test_rate_match_mapper()
+{
+  const ldpc_hip_rm_desc  rd{32, 96, 66 * 384, 30000, 0, 100, 8, 2};
+  const ldpc_hip_mod_desc md = mod_desc(8, 3750, true);
+  /* the pair is the rate matcher's item and the mapper's, each as translated alone */
+  rm_mod_cb    cb;
+  ratematch_cb r;
+  mod_seg      g;
+  uint64_t     blocks = 7, blocks_alone = 7;
+  std::memset(&cb, 0xa5, sizeof(cb));
+  CHECK(make_rm_mod_cb(rd, md, blocks, cb) == nullptr);
+  CHECK(make_rm_cb(rd, r) == nullptr && make_mod_seg(md, blocks_alone, g) == nullptr);
+  CHECK(std::memcmp(&cb.rm, &r, sizeof(r)) == 0 && std::memcmp(&cb.mod, &g, sizeof(g)) == 0);
+  CHECK(blocks == blocks_alone && blocks == 7 + 4 && cb.mod.block0 == 7); /* 938 chunks of 4 symbols */
+  /* the pair's own reasons */
+  ldpc_hip_rm_desc  r1{0, 0, 50 * 36, 1248, 0, 0, 1, 0};
+  ldpc_hip_mod_desc m1 = mod_desc(LDPC_HIP_MOD_PI_2_BPSK, 1248, false);
+  REASON(make_rm_mod_cb(r1, m1, blocks, cb), R_RMMOD_BPSK);
+  m1.modulation = LDPC_HIP_MOD_BPSK;
+  CHECK(make_rm_mod_cb(r1, m1, blocks, cb) == nullptr);
+  ldpc_hip_mod_desc m = md;
+  m.nof_symbols       = 3749;
+  REASON(make_rm_mod_cb(rd, m, blocks, cb), R_RMMOD_PAIR);
+  m = mod_desc(6, 5000, true); /* 30000 bits, but not the rate matcher's interleaving */
+  REASON(make_rm_mod_cb(rd, m, blocks, cb), R_RMMOD_PAIR);
+  ldpc_hip_rm_desc r2 = rd;
+  r2.modulation_order = 2, r2.rm_length = 0x80000000U;
+  REASON(make_rm_mod_cb(r2, mod_desc(2, 0x40000000U, true), blocks, cb), R_RMMOD_PAIR);
+  /* order: the rate matcher, the mapper, pi/2-BPSK, the pair's lengths */
+  m1.modulation = LDPC_HIP_MOD_PI_2_BPSK, m1.nof_symbols = 1247;
+  REASON(make_rm_mod_cb(r1, m1, blocks, cb), R_RMMOD_BPSK);
+  m1.scramble = 1;
+  REASON(make_rm_mod_cb(r1, m1, blocks, cb), R_MOD_CINIT);
+  r1.rv = 4;
+  REASON(make_rm_mod_cb(r1, m1, blocks, cb), R_RM_PARAMS);
+}
+
+static ldpc_hip_eq_desc eq_desc(int algorithm, unsigned ports, unsigned layers, uint32_t nof_re, uint64_t stride)
+{
+  ldpc_hip_eq_desc d{};
+  d.sym_offset    = 3;
+  d.sym_stride    = stride;
+  d.est_offset    = 17;
+  d.est_stride    = stride + 1;
+  d.out_offset    = 29;
+  d.nof_re        = nof_re;
+  d.tx_scaling    = 0.5f;
+  d.algorithm     = static_cast<uint8_t>(algorithm);
+  d.nof_rx_ports  = static_cast<uint8_t>(ports);
+  d.nof_tx_layers = static_cast<uint8_t>(layers);
+  for (int p = 0; p != 4; ++p) {
+    d.noise_var[p] = 0.25f * static_cast<float>(p + 1);
+  }
+  return d;
+}
+
+static void test_equalizer()
+{
+  /* a block equalises EQ_BLOCK x EQ_RES = 256 REs: 1025 REs are 5 blocks */
+  const ldpc_hip_eq_desc d[3] = {eq_desc(LDPC_HIP_EQ_MMSE, 1, 1, 5, 8), eq_desc(LDPC_HIP_EQ_ZF, 4, 1, 0, 0),
+                                 eq_desc(LDPC_HIP_EQ_ZF, 4, 2, 1025, 2000)};
+  std::vector<eq_seg>    sg;
+  uint32_t               nblocks = 0;
+  CHECK(make_eq_segs(3, d, sg, nblocks) == nullptr && sg.size() == 2 && nblocks == 6);
+  CHECK(sg[0].nof_re == 5 && sg[0].block0 == 0 && sg[0].sym_stride == 8 && sg[0].est_stride == 9);
+  CHECK(sg[0].algorithm == LDPC_HIP_EQ_MMSE && sg[0].nof_rx_ports == 1 && sg[0].nof_tx_layers == 1);
+  CHECK(sg[1].nof_re == 1025 && sg[1].block0 == 1 && sg[1].sym_stride == 2000 && sg[1].est_stride == 2001);
+  CHECK(sg[1].algorithm == LDPC_HIP_EQ_ZF && sg[1].nof_rx_ports == 4 && sg[1].nof_tx_layers == 2);
+  for (const eq_seg& g : sg) {
+    CHECK(g.sym_offset == 3 && g.est_offset == 17 && g.out_offset == 29 && g.tx_scaling == 0.5f && g.pad == 0);
+    CHECK(g.noise_var[0] == 0.25f && g.noise_var[1] == 0.5f && g.noise_var[2] == 0.75f && g.noise_var[3] == 1.0f);
+  }
+  uint64_t blocks = 9;
+  eq_seg   g;
+  CHECK(make_eq_seg(d[2], blocks, g) == nullptr && g.block0 == 9 && blocks == 14);
+  REASON(make_eq_seg(eq_desc(LDPC_HIP_EQ_MMSE, 2, 2, 5, 8), blocks, g), R_EQ_TOPOLOGY);
+  REASON(make_eq_seg(eq_desc(LDPC_HIP_EQ_ZF, 3, 2, 5, 8), blocks, g), R_EQ_TOPOLOGY);
+  REASON(make_eq_seg(eq_desc(2, 1, 1, 5, 8), blocks, g), R_EQ_TOPOLOGY);
+  ldpc_hip_eq_desc x = d[0];
+  for (const float bad : {0.0f, -1.0f, std::nanf("")}) {
+    x.tx_scaling = bad;
+    REASON(make_eq_seg(x, blocks, g), R_EQ_SCALING);
+  }
+  x = d[0], x.sym_stride = 4;
+  REASON(make_eq_seg(x, blocks, g), R_EQ_STRIDE);
+  x = d[0], x.est_stride = 4;
+  REASON(make_eq_seg(x, blocks, g), R_EQ_STRIDE);
+  x = eq_desc(LDPC_HIP_EQ_ZF, 2, 2, 0x40000000U, 0x40000000U);
+  REASON(make_eq_seg(x, blocks, g), R_EQ_SEG);
+  /* order: topology, scaling, strides, the segment's size; the empty segment is validated too */
+  x.sym_stride = 1;
+  REASON(make_eq_seg(x, blocks, g), R_EQ_STRIDE);
+  x.tx_scaling = std::nanf("");
+  REASON(make_eq_seg(x, blocks, g), R_EQ_SCALING);
+  x.algorithm = LDPC_HIP_EQ_MMSE;
+  REASON(make_eq_seg(x, blocks, g), R_EQ_TOPOLOGY);
+  CHECK(blocks == 14);
+  x = d[1], x.tx_scaling = 0.0f;
+  REASON(make_eq_segs(1, &x, sg, nblocks), R_EQ_SCALING);
+  /* 2^31 - 1 REs of one layer: 2^23 blocks */
+  check_block_cap<ldpc_hip_eq_desc, eq_seg>(eq_desc(LDPC_HIP_EQ_ZF, 1, 1, 0x7fffffffU, 0x7fffffffU), 255, 1U << 23,
+                                            R_EQ_MANY, make_eq_segs);
+}
+
 int main()
 {
   CHECK(align16(0) == 0 && align16(1) == 16 && align16(16) == 16 && align16(17) == 32);
@@ -489,6 +762,11 @@ int main()
   test_rate_matcher();
   test_pdsch();
   test_tb_join();
+  test_demodulator();
+  test_sequences();
+  test_mapper();
+  test_rate_match_mapper();
+  test_equalizer();
   std::printf(g_failed == 0 ? "test_descs: all passed\n" : "test_descs: %d checks failed\n", g_failed);
   return g_failed == 0 ? 0 : 1;
 }

@@ -138,6 +138,69 @@ def test_every_launch_entry_point_on_special_handle(hip_ctx, handle):
     np.testing.assert_array_equal(np.unpackbits(d_rm.cpu().numpy())[:E], O.rate_match(ref, E, 0, 2, 0, bg, Z))
 
 
+def test_new_descriptors_refused_inside_capture():
+    """A launch entry point inside a stream capture: descriptors that differ from the last upload are refused
+    (LDPC_HIP_EDEVICE, hipErrorStreamCaptureUnsupported through the launch's own message) and record nothing; the
+    descriptors launched before the capture are taken without a copy and recorded. The demodulator, one segment of 64
+    QPSK symbols (one block): A writes its 128 LLRs at offset 0, B differs in llr_offset = 128 only (same byte size, no
+    reallocation)."""
+    import ctypes
+    import torch
+    from srsran_projectvtlmo_amd import _lib
+    from srsran_projectvtlmo_amd import channel_modulation as cm
+    from tests.vectors import noisy_symbols
+    rng = np.random.default_rng(800)
+    _, sym, nv = noisy_symbols(rng, 64, 2, noise_var=0.1)
+    expect = O.demodulate_soft(2, sym, nv)
+    assert expect.size == 128
+    desc_a = cm.demod_descriptors([cm.demod_segment(64, 2, 0, 0, 0)])
+    desc_b = cm.demod_descriptors([cm.demod_segment(64, 2, 0, 0, 128)])
+    d_sym = torch.from_numpy(sym.view(np.float32)).cuda()
+    d_nv = torch.from_numpy(nv).cuda()
+    d_llr = torch.full((256,), 99, dtype=torch.int8, device="cuda")
+    side = torch.cuda.Stream()
+    stream = side.cuda_stream
+    torch.cuda.synchronize()
+    ctx = _lib.Context(0)
+    L, c = ctx.lib, ctx.handle
+    graph = ctypes.c_void_p()
+
+    def launch(desc):
+        return L.ldpc_hip_demodulate_launch(c, 1, desc, ctypes.c_void_p(d_sym.data_ptr()),
+                                            ctypes.c_void_p(d_nv.data_ptr()), ctypes.c_void_p(d_llr.data_ptr()),
+                                            ctypes.c_void_p(stream))
+    try:
+        # 1. eager, so that A is what the table holds
+        assert launch(desc_a) == _lib.OK
+        side.synchronize()
+        first = d_llr.cpu().numpy()[:128].copy()
+        assert np.array_equal(first, expect)
+        # 2. and 3. inside the capture: B refused, A recorded
+        assert L.ldpc_hip_capture_begin(c, ctypes.c_void_p(stream)) == _lib.OK
+        try:
+            rc_b = launch(desc_b)
+            msg_b = L.ldpc_hip_last_error(c).decode()
+            rc_a = launch(desc_a)
+        finally:
+            rc_end = L.ldpc_hip_capture_end(c, ctypes.c_void_p(stream), ctypes.byref(graph))
+        assert rc_b == _lib.EDEVICE
+        assert msg_b.startswith("ldpc_demodulate_kernel launch: "), msg_b
+        assert rc_a == _lib.OK
+        assert rc_end == _lib.OK and graph
+        # 4. the replay is A alone
+        d_llr.fill_(77)
+        torch.cuda.synchronize()
+        assert L.ldpc_hip_graph_launch(graph, ctypes.c_void_p(stream)) == _lib.OK
+        side.synchronize()
+        got = d_llr.cpu().numpy()
+        assert np.array_equal(got[:128], first)
+        assert np.all(got[128:] == 77), "the refused launch recorded a write"
+    finally:
+        if graph:
+            L.ldpc_hip_graph_destroy(graph)
+        ctx.close()
+
+
 def test_default_stream_launch_ordered_behind_fill():
     """Deterministic form of round 4's ordering race: behind a 1 GiB fill and add on torch's default stream, the
     launch's input copy and output fills are queued, then the decode is launched with stream 0 (the wrappers' "torch's
