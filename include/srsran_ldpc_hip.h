@@ -516,6 +516,53 @@ int ldpc_hip_equalize_sync(ldpc_hip_ctx* ctx, int algorithm, uint32_t nof_re, ui
                            uint32_t nof_tx_layers, const uint16_t* ch_symbols, const uint16_t* ch_estimates,
                            const float* noise_vars, float tx_scaling, float* eq_symbols, float* eq_noise_vars);
 
+/* ---- precoder: layer mapping and precoding of modulated symbols into the resource grid --------------------------
+ * resource_grid_mapper_impl::map(symbol_buffer&, ...) with re_skip == 0 (resource_grid_mapper_impl.cpp:293-436) over
+ * channel_precoder_generic.cpp:50-70 and resource_grid_writer_impl.cpp:44-81: the masked REs of a transmission in
+ * ascending (OFDM symbol, subcarrier) order, the r-th reading layer i at input[L r + i]; the PRG of subcarrier k is
+ * k / (12 prg_size), counted from grid subcarrier 0; per port sum = to_cf(x_0) w_0, then sum += to_cf(x_i) w_i in
+ * ascending i, in float32 with every product (ac - bd, ad + bc) uncontracted; cf32 to cbf16 rounds each component to
+ * nearest even on its bits. The grid REs are the reference's bit for bit (built without its SIMD loops). Topologies:
+ * every 1 <= layers <= ports <= 4. A weight component must be finite and below 2^64 in magnitude (the reference's
+ * complex multiply then never takes its NaN fall-back); cf32 layer inputs must be finite and as small, which is not
+ * checked. Weights carry the modulation scaling already: (re * s, im * s), as pdsch_modulator_impl.cpp:96-100 does. */
+/* Host only: 1 for the ten topologies, else 0. */
+int ldpc_hip_precode_supported(uint32_t nof_layers, uint32_t nof_ports);
+/* One row: one transmission on one OFDM symbol. Subcarrier k of the row is masked when bit k % 64 of word
+ * mask_offset + k / 64 of `masks` is set; rows with the same mask (data symbols against DM-RS symbols) share its
+ * words. The row's r-th masked subcarrier reads ci8 symbols sym_offset + L r .. + L - 1 and writes, per port p, the
+ * cbf16 element grid_offset + p port_stride + k. */
+typedef struct {            /* 48 bytes */
+  uint64_t sym_offset;      /* the row's first symbol, in ci8 elements (2 bytes) from d_symbols               */
+  uint64_t grid_offset;     /* port 0, subcarrier 0 of the row, in cbf16 elements (4 bytes) from d_grid        */
+  uint64_t port_stride;     /* cbf16 elements between ports, >= width                                          */
+  uint32_t mask_offset;     /* the row's first word in masks; ceil(width / 64) words, no bit at or past width   */
+  uint32_t weight_offset;   /* the transmission's weights [prg][port][layer], in cf32 elements from weights      */
+  uint32_t nof_prg;
+  uint32_t width;           /* subcarriers of the row                                                          */
+  uint16_t prg_size;        /* in resource blocks, >= 1                                                        */
+  uint8_t  nof_layers, nof_ports;
+  uint8_t  pad[4];
+} ldpc_hip_precode_desc;
+/* Precodes and maps nof_rows rows on device buffers in one launch, asynchronously on `stream` (NULL = the context
+ * stream). descs, weights (nof_weights cf32 elements, float re, im) and masks (nof_mask_words words) are host arrays;
+ * they are uploaded into a per-context table, which an equal call on the same stream reuses (so: launch once, then
+ * capture). d_symbols is aligned to 2 bytes and d_grid to 4; a row whose symbols or grid REs lie on wider boundaries
+ * takes wider loads and 16-byte stores. No byte outside a row's symbols is read and no grid byte outside its masked REs
+ * written; rows of different topologies may share a launch; a row with no masked RE is skipped. Two rows that overlap
+ * in the grid are the caller's error and are not detected. LDPC_HIP_EINVAL: a topology outside the ten, a refused
+ * weight, a masked subcarrier whose PRG lies outside the weight block, a row wider than its port stride, a mask or
+ * weight block outside its array, a mask bit at or past the width, prg_size 0, a null argument. */
+int ldpc_hip_precode_map_launch(ldpc_hip_ctx* ctx, uint32_t nof_rows, const ldpc_hip_precode_desc* descs,
+                                const float* weights, uint32_t nof_weights, const uint64_t* masks,
+                                uint32_t nof_mask_words, const void* d_symbols, void* d_grid, void* stream);
+/* channel_precoder on host buffers, one PRG: weights [port][layer] (cf32); output [port][re] (cf32, contiguous).
+ * input_format LDPC_HIP_SYM_CI8: apply_layer_map_and_precoding of nof_re * nof_layers interleaved ci8 symbols;
+ * LDPC_HIP_SYM_CF32: apply_precoding of layer planes [layer][re] (channel_precoder_impl.cpp:27-70,
+ * channel_precoder_generic.cpp:27-48). LDPC_HIP_EINVAL also for nof_re * nof_layers >= 2^31. */
+int ldpc_hip_precode_sync(ldpc_hip_ctx* ctx, uint32_t nof_re, uint32_t nof_layers, uint32_t nof_ports,
+                          const void* input, int input_format, const float* weights, float* output);
+
 /* ---- launch graphs: one submission per slot ---------------------------------------------------------------- */
 /* srsRAN runs the PUSCH decode chain once per slot with the same shape slot after slot (pusch_decoder_impl /
  * pusch_decoder_hw_impl call the decoder per codeblock and join per TB). Here the chain's *_launch calls on `stream`

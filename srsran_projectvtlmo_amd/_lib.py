@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "ldpc_hip_modulation_scaling", "ldpc_hip_modulate_launch", "ldpc_hip_modulate_sync",
     "ldpc_hip_rate_match_modulate_launch",
     "ldpc_hip_equalize_supported", "ldpc_hip_equalize_launch", "ldpc_hip_equalize_sync",
+    "ldpc_hip_precode_supported", "ldpc_hip_precode_map_launch", "ldpc_hip_precode_sync",
 ]
 SYM_CF32, SYM_CI8 = 0, 1   # LDPC_HIP_SYM_*
 EQ_ZF, EQ_MMSE = 0, 1      # LDPC_HIP_EQ_*
@@ -174,6 +175,17 @@ class EqDesc(ctypes.Structure):
 assert ctypes.sizeof(EqDesc) == 72
 
 
+class PrecodeDesc(ctypes.Structure):
+    """ldpc_hip_precode_desc (include/srsran_ldpc_hip.h)."""
+    _fields_ = [("sym_offset", ctypes.c_uint64), ("grid_offset", ctypes.c_uint64), ("port_stride", ctypes.c_uint64),
+                ("mask_offset", ctypes.c_uint32), ("weight_offset", ctypes.c_uint32), ("nof_prg", ctypes.c_uint32),
+                ("width", ctypes.c_uint32), ("prg_size", ctypes.c_uint16), ("nof_layers", ctypes.c_uint8),
+                ("nof_ports", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 4)]
+
+
+assert ctypes.sizeof(PrecodeDesc) == 48
+
+
 class TbResult(ctypes.Structure):
     _fields_ = [("tb_crc_ok", ctypes.c_uint8), ("written", ctypes.c_uint8), ("nof_cbs_ok", ctypes.c_uint16)]
 
@@ -257,6 +269,9 @@ def load():
         "ldpc_hip_equalize_supported": (I, [I, U32, U32]),
         "ldpc_hip_equalize_launch": (I, [P, U32, ctypes.POINTER(EqDesc), P, P, P, P, P]),
         "ldpc_hip_equalize_sync": (I, [P, I, U32, U32, U32, P, P, P, ctypes.c_float, P, P]),
+        "ldpc_hip_precode_supported": (I, [U32, U32]),
+        "ldpc_hip_precode_map_launch": (I, [P, U32, ctypes.POINTER(PrecodeDesc), P, U32, P, U32, P, P, P]),
+        "ldpc_hip_precode_sync": (I, [P, U32, U32, U32, P, I, P, P]),
         "ldpc_hip_capture_begin": (I, [P, P]),
         "ldpc_hip_capture_end": (I, [P, P, ctypes.POINTER(P)]),
         "ldpc_hip_graph_launch": (I, [P, P]),

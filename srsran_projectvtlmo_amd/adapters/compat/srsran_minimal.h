@@ -353,6 +353,69 @@ public:
   virtual std::unique_ptr<channel_equalizer> create() = 0;
 };
 
+/* re_buffer.h:36-73 (the interfaces only), precoding_weight_matrix.h (layer the fastest index, as its tensor),
+ * channel_precoder.h:34-64, precoding_factories.h:34-42 */
+namespace detail {
+class re_buffer_dimensions
+{
+public:
+  virtual ~re_buffer_dimensions()         = default;
+  virtual unsigned get_nof_slices() const = 0;
+  virtual unsigned get_nof_re() const     = 0;
+};
+} // namespace detail
+class re_buffer_reader : public detail::re_buffer_dimensions
+{
+public:
+  virtual span<const cf_t> get_slice(unsigned i_slice) const = 0;
+};
+class re_buffer_writer : public detail::re_buffer_dimensions
+{
+public:
+  virtual span<cf_t> get_slice(unsigned i_slice) = 0;
+};
+class precoding_weight_matrix
+{
+public:
+  precoding_weight_matrix() = default;
+  precoding_weight_matrix(unsigned nof_layers_, unsigned nof_ports_) :
+    nof_layers(nof_layers_), nof_ports(nof_ports_), data(static_cast<std::size_t>(nof_layers_) * nof_ports_)
+  {
+  }
+  unsigned         get_nof_layers() const { return nof_layers; }
+  unsigned         get_nof_ports() const { return nof_ports; }
+  span<const cf_t> get_port_coefficients(unsigned i_port) const
+  {
+    return span<const cf_t>(data.data() + static_cast<std::size_t>(i_port) * nof_layers, nof_layers);
+  }
+  cf_t get_coefficient(unsigned i_layer, unsigned i_port) const { return data[i_port * nof_layers + i_layer]; }
+  void set_coefficient(cf_t coefficient, unsigned i_layer, unsigned i_port)
+  {
+    data[i_port * nof_layers + i_layer] = coefficient;
+  }
+
+private:
+  unsigned          nof_layers = 0, nof_ports = 0;
+  std::vector<cf_t> data;
+};
+class channel_precoder
+{
+public:
+  virtual ~channel_precoder() = default;
+  virtual void apply_precoding(re_buffer_writer&              output,
+                               const re_buffer_reader&        input,
+                               const precoding_weight_matrix& precoding) const = 0;
+  virtual void apply_layer_map_and_precoding(re_buffer_writer&              output,
+                                             span<const ci8_t>              input,
+                                             const precoding_weight_matrix& precoding) const = 0;
+};
+class channel_precoder_factory
+{
+public:
+  virtual ~channel_precoder_factory()                = default;
+  virtual std::unique_ptr<channel_precoder> create() = 0;
+};
+
 namespace dpdk {
 class bbdev_acc; /* include/srsran/hal/dpdk/bbdev/bbdev_acc.h: the DPDK bbdev accelerator (not used by "mi355x") */
 }

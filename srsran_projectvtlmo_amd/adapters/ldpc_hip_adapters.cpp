@@ -348,6 +348,77 @@ srsran::create_channel_equalizer_factory_hip(channel_equalizer_algorithm_type ty
   return std::make_shared<channel_equalizer_factory_hip>(type, device);
 }
 
+/* ---- channel precoder ---- */
+void channel_precoder_hip::run(re_buffer_writer&              output,
+                               const void*                    input,
+                               int                            format,
+                               const precoding_weight_matrix& precoding) const
+{
+  const unsigned nof_re = output.get_nof_re(), nof_ports = output.get_nof_slices();
+  const unsigned nof_layers = precoding.get_nof_layers();
+  srsran_assert(nof_ports == precoding.get_nof_ports(),
+                "The number on TX ports on the output buffer does not match the precoding matrix.");
+  srsran_assert(ldpc_hip_precode_supported(nof_layers, nof_ports) == 1, "Invalid number of layers and ports.");
+  static_assert(sizeof(ci8_t) == 2 && sizeof(cf_t) == 8, "ci8_t is two int8, cf_t two floats");
+  std::vector<cf_t> weights, out(static_cast<std::size_t>(nof_re) * nof_ports);
+  for (unsigned p = 0; p != nof_ports; ++p) {
+    span<const cf_t> w = precoding.get_port_coefficients(p);
+    weights.insert(weights.end(), w.begin(), w.end());
+  }
+  check_rc(ctx.get(),
+           ldpc_hip_precode_sync(ctx.get(), nof_re, nof_layers, nof_ports, input, format,
+                                 reinterpret_cast<const float*>(weights.data()), reinterpret_cast<float*>(out.data())));
+  for (unsigned p = 0; p != nof_ports; ++p) {
+    span<cf_t> slice = output.get_slice(p);
+    std::copy(out.begin() + static_cast<std::size_t>(p) * nof_re, out.begin() + static_cast<std::size_t>(p + 1) * nof_re,
+              slice.begin());
+  }
+}
+
+void channel_precoder_hip::apply_precoding(re_buffer_writer&              output,
+                                           const re_buffer_reader&        input,
+                                           const precoding_weight_matrix& precoding) const
+{
+  /* channel_precoder_impl.cpp:36-57 */
+  const unsigned nof_re = output.get_nof_re(), nof_layers = input.get_nof_slices();
+  srsran_assert(nof_re == input.get_nof_re(), "The number of output RE per slice does not match the input's.");
+  srsran_assert(nof_layers == precoding.get_nof_layers(),
+                "The number on layers on the input buffer does not match the precoding matrix.");
+  std::vector<cf_t> in;
+  in.reserve(static_cast<std::size_t>(nof_re) * nof_layers);
+  for (unsigned l = 0; l != nof_layers; ++l) {
+    span<const cf_t> slice = input.get_slice(l);
+    in.insert(in.end(), slice.begin(), slice.end());
+  }
+  run(output, in.data(), LDPC_HIP_SYM_CF32, precoding);
+}
+
+void channel_precoder_hip::apply_layer_map_and_precoding(re_buffer_writer&              output,
+                                                         span<const ci8_t>              input,
+                                                         const precoding_weight_matrix& precoding) const
+{
+  srsran_assert(input.size() == static_cast<std::size_t>(output.get_nof_re()) * precoding.get_nof_layers(),
+                "The number of input symbols does not match the output RE and the layers.");
+  run(output, input.data(), LDPC_HIP_SYM_CI8, precoding);
+}
+
+namespace {
+class channel_precoder_factory_hip : public channel_precoder_factory
+{
+public:
+  explicit channel_precoder_factory_hip(int dev) : device(dev) {}
+  std::unique_ptr<channel_precoder> create() override { return std::make_unique<channel_precoder_hip>(device); }
+
+private:
+  int device;
+};
+} // namespace
+
+std::shared_ptr<channel_precoder_factory> srsran::create_channel_precoder_factory_hip(int device)
+{
+  return std::make_shared<channel_precoder_factory_hip>(device);
+}
+
 /* ---- HAL ---- */
 using namespace srsran::hal;
 

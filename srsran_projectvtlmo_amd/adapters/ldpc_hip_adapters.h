@@ -6,6 +6,7 @@
  *   srsran::modulation_mapper_hip       : modulation_mapper    (modulation_mapper.h:35-64)    channel_modulation_factory
  *   srsran::demodulation_mapper_hip     : demodulation_mapper  (demodulation_mapper.h:46-70)  channel_modulation_factory
  *   srsran::channel_equalizer_hip       : channel_equalizer    (channel_equalizer.h:37-102)   channel_equalizer_factory
+ *   srsran::channel_precoder_hip        : channel_precoder     (channel_precoder.h:34-64)     channel_precoder_factory
  *   srsran::hal::hw_accelerator_pusch_dec_hip : hal::hw_accelerator_pusch_dec (hw_accelerator_pusch_dec.h:83-115)
  *                                                                                       acc_type "mi355x"
  *   srsran::hal::hw_accelerator_pdsch_enc_hip : hal::hw_accelerator_pdsch_enc (hw_accelerator_pdsch_enc.h:75-102)
@@ -26,6 +27,7 @@
 #ifdef SRSRAN_LDPC_HIP_IN_TREE
 #include "srsran/hal/phy/upper/channel_processors/hw_accelerator_pdsch_enc_factory.h"
 #include "srsran/hal/phy/upper/channel_processors/pusch/hw_accelerator_pusch_dec_factory.h"
+#include "srsran/phy/generic_functions/precoding/precoding_factories.h"
 #include "srsran/phy/upper/channel_coding/channel_coding_factories.h"
 #include "srsran/phy/upper/channel_modulation/channel_modulation_factories.h"
 #include "srsran/phy/upper/equalization/equalization_factories.h"
@@ -190,6 +192,28 @@ private:
 std::shared_ptr<channel_equalizer_factory>
 create_channel_equalizer_factory_hip(channel_equalizer_algorithm_type type = channel_equalizer_algorithm_type::zf,
                                      int                              device = 0);
+
+/* The channel precoder on the GPU: the reference's generic loops (channel_precoder_generic.cpp:27-70) bit for bit,
+ * through ldpc_hip_precode_sync, for every 1 <= layers <= ports <= 4; anything else asserts. The buffers' slices need
+ * not be contiguous: they are gathered into planes on the host. */
+class channel_precoder_hip : public channel_precoder
+{
+public:
+  explicit channel_precoder_hip(int device = 0) : ctx(device) {}
+  void apply_precoding(re_buffer_writer&              output,
+                       const re_buffer_reader&        input,
+                       const precoding_weight_matrix& precoding) const override;
+  void apply_layer_map_and_precoding(re_buffer_writer&              output,
+                                     span<const ci8_t>              input,
+                                     const precoding_weight_matrix& precoding) const override;
+
+private:
+  void run(re_buffer_writer& output, const void* input, int format, const precoding_weight_matrix& precoding) const;
+  ldpc_hip_context ctx;
+};
+
+/* The factory create_channel_precoder_factory("generic") stands for. */
+std::shared_ptr<channel_precoder_factory> create_channel_precoder_factory_hip(int device = 0);
 
 namespace hal {
 
