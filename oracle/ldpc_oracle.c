@@ -493,6 +493,11 @@ int orc_rate_dematch(int8_t* out, unsigned cb_len, const int8_t* in, unsigned E,
   if (nof_filler_bits >= nof_systematic) {
     return -1;
   }
+  /* a buffer shorter than the systematic part would wrap buffer_length - tmp_idx below (the reference leaves it to a
+   * subspan assert; no TS 38.212 configuration produces it). buffer_length == nof_systematic is legal. */
+  if (buffer_length < nof_systematic) {
+    return -1;
+  }
   unsigned shift_k0 = (unsigned)floor((shift_factor[rv] * buffer_length) / block_length) * Z; /* :104-105 */
 
   /* deinterleave_bits_Qm (:203-213): out[(E/Qm)*j + i] = in[i*Qm + j] */

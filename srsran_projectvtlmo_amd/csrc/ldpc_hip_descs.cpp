@@ -181,6 +181,12 @@ const char* make_dematch_cb(const ldpc_hip_dematch_desc& s, const int8_t* llr, i
   if (s.nof_filler_bits >= (K - 2) * Z) {
     return "LDPC rate dematching: invalid number of filler bits.";
   }
+  /* a limited buffer covers the systematic bits in every TS 38.212 configuration; a shorter one would make the allot
+   * loop's parity range (Ncb - tmp_idx after tmp_idx was raised to (K - 2) Z) wrap and write past the soft buffer.
+   * Ncb == (K - 2) Z is legal: that range is empty and the loop still ends */
+  if (s.Nref != 0 && std::min<unsigned>(s.Nref, s.cb_length) < (K - 2) * Z) {
+    return "LDPC rate dematching: limited buffer shorter than the systematic bits.";
+  }
   /* the fused dematcher writes cb_length soft bits at the decode descriptor's offset, inside the workgroup that then
    * decodes them: a length or filler mismatch would write into a neighbour's buffer while it is being decoded */
   if (paired != nullptr && (s.cb_length != paired->llr_length || s.nof_filler_bits != paired->nof_filler_bits)) {

@@ -2,6 +2,7 @@
  * descriptors, one rejection per reason, the order of the checks, and the one-CB / plan equivalence. Links the
  * host-only units alone (no HIP runtime); built with AddressSanitizer and UBSan by tests/test_descs_host.py.
  * The expected reasons are the texts of the entry points' errors before the translations were gathered in one unit. */
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -41,6 +42,7 @@ static const char* const R_DM_PARAMS  = "invalid rv / modulation / rm_length";
 static const char* const R_DM_LARGE   = "N_ref / cb_length too large";
 static const char* const R_DM_LEN     = "LDPC rate dematching: invalid input length.";
 static const char* const R_DM_FILL    = "LDPC rate dematching: invalid number of filler bits.";
+static const char* const R_DM_NCB     = "LDPC rate dematching: limited buffer shorter than the systematic bits.";
 static const char* const R_DM_PAIRED  = "dematch_decode_launch: dematch descriptor does not match its codeblock "
                                         "(cb_length != llr_length or filler bits differ)";
 /* the one wording of what were "demod_dematch_launch: symbols x bits per symbol must equal rm_length",
@@ -378,6 +380,42 @@ static void test_dematch_rejections()
   REASON(dematch(s, c, &m, &scr, &cb), R_DM_PARAMS);
   m.nof_symbols = 16392;
   REASON(dematch(dm_desc(1, 384, 2, 32784), c, &m, &scr), R_DM_DEMOD); /* the demodulator before scrambling */
+}
+
+/* a limited buffer must cover the systematic bits: Ncb = (K - 2) Z - 1 would wrap the allot loop's parity range
+ * (Ncb - tmp_idx with tmp_idx raised to (K - 2) Z) and write past the soft buffer; Ncb = (K - 2) Z is the legal edge */
+static void test_dematch_buffer_boundary()
+{
+  const struct {
+    int      bg;
+    unsigned Z, K;
+  } graphs[] = {{1, 2, 22}, {1, 384, 22}, {2, 2, 10}, {2, 36, 10}, {2, 384, 10}};
+  for (const auto& g : graphs) {
+    const unsigned        nsys = (g.K - 2) * g.Z;
+    ldpc_hip_dematch_desc s    = dm_desc(g.bg, g.Z, 2, 2 * g.Z + 6);
+    s.nof_filler_bits          = g.Z / 2;
+    dematch_cb c;
+    s.Nref = nsys - 1;
+    REASON(dematch(s, c), R_DM_NCB);
+    s.Nref = 1;
+    REASON(dematch(s, c), R_DM_NCB);
+    for (const unsigned nref : {nsys, nsys + 1, s.cb_length, std::min(s.cb_length + 7U, 66U * 384U)}) {
+      s.Nref = nref;
+      std::memset(static_cast<void*>(&c), 0xa5, sizeof(c));
+      CHECK(dematch(s, c) == nullptr);
+      CHECK(c.Nref == nref && c.cb_length == s.cb_length && c.rm_length == 2 * g.Z + 6 && c.modulation_order == 2);
+      CHECK(c.nof_filler_bits == g.Z / 2 && c.rv == 2 && c.new_data == 1 && c.sym == nullptr && c.scr_x1 == 0);
+    }
+    /* the refusal comes after the filler check and before the fused pair's */
+    s.Nref = nsys - 1, s.nof_filler_bits = nsys;
+    REASON(dematch(s, c), R_DM_FILL);
+    s.nof_filler_bits = g.Z / 2;
+    dec_cb                  cb;
+    const ldpc_hip_dec_desc dd = dec_desc(g.bg, g.Z);
+    CHECK(make_dec_cb(dd, cb) == nullptr);
+    cb.nof_filler_bits = static_cast<uint16_t>(g.Z / 2 + 1);
+    REASON(dematch(s, c, nullptr, nullptr, &cb), R_DM_NCB);
+  }
 }
 
 static void test_encoder()
@@ -758,6 +796,7 @@ int main()
   test_hw_config();
   test_dematch_valid();
   test_dematch_rejections();
+  test_dematch_buffer_boundary();
   test_encoder();
   test_rate_matcher();
   test_pdsch();

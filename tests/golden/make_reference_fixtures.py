@@ -1,4 +1,5 @@
-"""Records tests/golden/ref_*.npz from the compiled reference (oracle/_ref/libsrsran_ref.so, `make -C oracle ref`).
+"""Records tests/golden/ref_*.npz and ref_dematch_grid.json (digests only) from the compiled reference
+(oracle/_ref/libsrsran_ref.so, `make -C oracle ref`).
 
     python tests/golden/make_reference_fixtures.py
 
@@ -43,8 +44,23 @@ def record(op, cases, inputs, stored=False):
     return outs
 
 
+def record_dematch_grid():
+    """tests/golden/ref_dematch_grid.json: per case of tests/dematch_grid.py its numbers and one SHA-256 over the three
+    soft buffers the reference wrote (no buffer is stored: the full-size graphs' would not fit)."""
+    import json
+    from tests.dematch_grid import grid_cases
+    cases = grid_cases()
+    doc = {"keys": list(C.DEMATCH_GRID_KEYS), "cases": [[c[k] for k in C.DEMATCH_GRID_KEYS] for c in cases],
+           "sha256": [C.dematch_grid_digest(ref, c) for c in cases]}
+    path = C.GOLDEN / "ref_dematch_grid.json"
+    path.write_text(json.dumps(doc, separators=(",", ":")) + "\n")
+    assert path.stat().st_size <= MAX_BYTES, f"{path.name}: {path.stat().st_size} bytes"
+    print(f"{path.name}: {len(cases)} cases, {path.stat().st_size} bytes")
+
+
 def main():
     assert ref.available(), "build oracle/_ref first: make -C oracle ref"
+    record_dematch_grid()
     for op, cases in (("decode", C.fixture_decode_cases()), ("decode_sf", C.fixture_decode_sf_cases()),
                       ("dematch", C.fixture_dematch_cases()), ("chain", C.chain_cases()),
                       ("demod", C.demod_cases(257)), ("descramble", C.descramble_cases()),

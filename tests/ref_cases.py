@@ -214,7 +214,26 @@ def live_dematch_cases():
     for i, (E, rv, Qm, nref, lbrm, F) in enumerate(REF_TABLE):
         for j, (bg, Z) in enumerate(RM_GRAPHS):
             cases.append(dematch_case(bg, Z, E, rv, Qm, F, nref if lbrm else 0, 22000 + 10 * i + 3 * j))
-    return cases
+    # every branch of the allot loop on graphs of every decoder body, and E / Qm around every workgroup width
+    # (tests/dematch_grid.py). The reference accepts every row, the empty transmission included.
+    from tests.dematch_grid import grid_cases
+    return cases + grid_cases()
+
+
+def dematch_grid_digest(impl, c) -> str:
+    """One SHA-256 over a grid case's three results (tests/golden/ref_dematch_grid.json records the reference's)."""
+    r = run_dematch(impl, c, dematch_input(c))
+    return digest(r["soft_new"], r["soft_comb"], r["soft_comb0"])
+
+
+DEMATCH_GRID_KEYS = ("bg", "Z", "E", "rv", "Qm", "F", "Nref", "seed", "row", "kind")
+
+
+def load_dematch_grid():
+    """[(case, recorded digest)] of tests/golden/ref_dematch_grid.json: case numbers and digests only."""
+    d = json.loads((Path(__file__).resolve().parent / "golden" / "ref_dematch_grid.json").read_text())
+    assert d["keys"] == list(DEMATCH_GRID_KEYS)
+    return [(dict(zip(d["keys"], row)), sha) for row, sha in zip(d["cases"], d["sha256"])]
 
 
 def fixture_dematch_cases():

@@ -227,3 +227,79 @@ def test_enqueue(hip_ctx, cb):
         lib.ldpc_hip_queue_free(h)
     assert np.array_equal(soft, cb["soft"])
     assert np.array_equal(out, cb["msg"])
+
+
+NCB_TEXT = "LDPC rate dematching: limited buffer shorter than the systematic bits."
+NSYS = (O.BG_K[BG] - 2) * Z
+
+
+@pytest.mark.parametrize("entry", ["rate_dematch_sync_1", "rate_dematch_sync_2", "rate_dematch_launch",
+                                   "rate_dematch_scr_launch", "demod_dematch_launch", "dematch_decode_launch",
+                                   "dematch_decode_scr_launch", "enqueue"])
+def test_limited_buffer_below_systematic_bits(hip_ctx, cb, entry):
+    """Nref = (K - 2) Z - 1 through every entry point that takes dematch descriptors: EINVAL with the reason, nothing
+    launched (the sentinel-filled soft buffer and output keep their bytes). With such a buffer the allot loop's parity
+    range would wrap and write up to E soft bits past the codeblock; the case is refused, never run."""
+    import torch
+    from srsran_projectvtlmo_amd import _lib
+    from srsran_projectvtlmo_amd import channel_modulation as cm
+    from srsran_projectvtlmo_amd import sequence_generators as sg
+    lib, h = hip_ctx.lib, hip_ctx.handle
+    bad = _dm_desc(Nref=NSYS - 1)
+    llr = np.array(cb["llr"])
+    zero = (ctypes.c_uint64 * 1)(0)
+    if entry.startswith("rate_dematch_sync"):
+        n = int(entry[-1])
+        softs = [np.full(N, 55, np.int8) for _ in range(n)]
+        descs = [_dm_desc() for _ in range(n - 1)] + [bad]
+        rc = lib.ldpc_hip_rate_dematch_sync(h, n, _arr(_lib.DematchDesc, descs), _ptrs(softs), _ptrs([llr] * n))
+        _rejected(hip_ctx, rc, NCB_TEXT)
+        assert all(np.all(s == 55) for s in softs)
+        return
+    if entry == "enqueue":
+        cfg = _lib.HwConfig(base_graph=BG, modulation_order=QM, rv=0, new_data=1, nof_segments=1, cw_length=E,
+                            lifting_size=Z, Ncb=N, Nref=NSYS - 1, nof_segment_bits=O.BG_K[BG] * Z, nof_filler_bits=0,
+                            max_nof_ldpc_iterations=ITERS, use_early_stop=0, cb_crc_type=_lib.CRC24B, cb_crc_len=24,
+                            absolute_cb_id=0)
+        assert lib.ldpc_hip_queue_reserve(h) == 0
+        try:
+            rc = lib.ldpc_hip_enqueue(h, 0, ctypes.byref(cfg), llr.ctypes.data, llr.size, None, 0)
+            _rejected(hip_ctx, rc, "invalid HAL operation configuration")  # the HAL has one text for its configuration
+        finally:
+            lib.ldpc_hip_queue_free(h)
+        return
+    d_llr = torch.from_numpy(llr).cuda()
+    d_soft = torch.full((NA + 64,), 55, dtype=torch.int8, device="cuda")
+    d_out = torch.full((MB + 16,), 55, dtype=torch.uint8, device="cuda")
+    nsym = E // QM
+    d_sym = torch.zeros(2 * nsym, dtype=torch.float32, device="cuda")
+    d_nv = torch.ones(nsym, dtype=torch.float32, device="cuda")
+    demod = cm.demod_descriptors([cm.demod_segment(nsym, QM, 0, 0, 0)])
+    scr = sg.scramble_descriptors([(0x2468ace, 0)])
+    descs = _arr(_lib.DematchDesc, [bad])
+    st = _lib.stream_arg(0)
+    plan = ctypes.c_void_p()
+    try:
+        if entry == "rate_dematch_launch":
+            rc = lib.ldpc_hip_rate_dematch_launch(h, 1, descs, d_llr.data_ptr(), zero, d_soft.data_ptr(), zero, st)
+        elif entry == "rate_dematch_scr_launch":
+            rc = lib.ldpc_hip_rate_dematch_scr_launch(h, 1, descs, d_llr.data_ptr(), zero, None, None, None, scr,
+                                                      d_soft.data_ptr(), zero, st)
+        elif entry == "demod_dematch_launch":
+            rc = lib.ldpc_hip_demod_dematch_launch(h, 1, descs, demod, d_sym.data_ptr(), d_nv.data_ptr(),
+                                                   d_soft.data_ptr(), zero, st)
+        else:
+            assert lib.ldpc_hip_decode_plan_create(h, 1, _arr(_lib.DecDesc, [_dec_desc()]), ctypes.byref(plan)) == 0
+            if entry == "dematch_decode_launch":
+                rc = lib.ldpc_hip_dematch_decode_launch(plan, descs, d_llr.data_ptr(), zero, None, None, None,
+                                                        d_soft.data_ptr(), d_out.data_ptr(), None, st)
+            else:
+                rc = lib.ldpc_hip_dematch_decode_scr_launch(plan, descs, None, None, demod, d_sym.data_ptr(),
+                                                            d_nv.data_ptr(), scr, d_soft.data_ptr(), d_out.data_ptr(),
+                                                            None, st)
+        _rejected(hip_ctx, rc, NCB_TEXT)
+        torch.cuda.synchronize()
+        assert bool((d_soft == 55).all()) and bool((d_out == 55).all())
+    finally:
+        if plan.value:
+            lib.ldpc_hip_decode_plan_destroy(plan)

@@ -163,7 +163,9 @@ def _dematch_descs(bg, Z, Qm, E, rv, new_data, n=2):
 @pytest.mark.parametrize("bg,Z,Qm,E", FUSED_SHAPES)
 @pytest.mark.parametrize("from_symbols", [False, True])
 def test_fused_dematch_descrambles(hip_ctx, bg, Z, Qm, E, from_symbols):
-    """Two CBs of one codeword (the second one's sequence offset is the first one's E), rv 0 with new data and then rv 2
+    """Descrambling fused into the stand-alone dematch kernel (ldpc_hip_rate_dematch_scr_launch, 512 threads): not the
+    dematcher fused into the decode kernels, whose soft buffers tests/test_gpu_dematch_grid.py compares.
+    Two CBs of one codeword (the second one's sequence offset is the first one's E), rv 0 with new data and then rv 2
     combining: the soft buffers equal the oracle dematcher fed the reference-descrambled LLRs; the LLRs come from
     d_llr, or are demodulated from symbols in the dematcher (oracle demodulator)."""
     import torch
