@@ -25,6 +25,7 @@
  * 4 L symbols and 4 L variances in 16-byte stores under the same rule. Nothing outside a segment's planes is read and
  * nothing outside its nof_re x layers outputs written. No LDS, no scratch.
  */
+#include "ldpc_block_item.h"
 #include "ldpc_equalize.h"
 
 #pragma clang fp contract(off)
@@ -282,17 +283,7 @@ __global__ void __launch_bounds__(EQ_BLOCK)
     ldpc_equalize_kernel(const eq_seg* __restrict__ segs, uint32_t nseg, const uint32_t* __restrict__ syms,
                          const uint32_t* __restrict__ ests, float* __restrict__ eq_syms, float* __restrict__ eq_nvs)
 {
-  /* this block's segment: the last one with block0 <= blockIdx.x (segments are in block order) */
-  uint32_t lo = 0, hi = nseg;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) / 2;
-    if (segs[mid].block0 <= blockIdx.x) {
-      lo = mid;
-    } else {
-      hi = mid;
-    }
-  }
-  const eq_seg   sg = segs[lo];
+  const eq_seg   sg = segs[block_item(segs, nseg)];
   const uint32_t g  = ((blockIdx.x - sg.block0) * EQ_BLOCK + threadIdx.x) * EQ_RES;
   /* block-uniform; the host admits these ten only */
   switch (sg.algorithm * 8U + (sg.nof_tx_layers - 1U) * 4U + (sg.nof_rx_ports - 1U)) {

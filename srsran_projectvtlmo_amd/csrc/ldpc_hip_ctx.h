@@ -2,8 +2,11 @@
  * The host runtime's shared state behind the C ABI of include/srsran_ldpc_hip.h: the context, decode plans, the HAL
  * queue's operations and the external HARQ repository, with the functions its units call across each other:
  * ldpc_hip_api.cpp (context, plans, *_launch entry points), ldpc_hip_sync.cpp (synchronous entry points),
- * ldpc_hip_modulate.cpp (modulation mapper), ldpc_hip_equalize.cpp (channel equalizer), ldpc_hip_precode.cpp (precoder), ldpc_hip_hal.cpp (HAL decoder
- * queue), ldpc_hip_enc_queue.cpp (PDSCH encoder queue) and ldpc_hip_descs.cpp (descriptor translations, host only).
+ * ldpc_hip_modulate.cpp (modulation mapper), ldpc_hip_equalize.cpp (channel equalizer), ldpc_hip_precode.cpp
+ * (precoder), ldpc_hip_hal.cpp (HAL decoder queue), ldpc_hip_enc_queue.cpp (PDSCH encoder queue) and
+ * ldpc_hip_descs.cpp (descriptor translations, the precoder's table among them, host only). The segment stages share
+ * the two tails here: launch_items (work items up, one launch) and sync_round_trip (a *_sync call's host buffers
+ * through the scratch).
  */
 #pragma once
 
@@ -11,6 +14,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
@@ -151,6 +155,22 @@ inline hipStream_t abi_stream(hipStream_t ctx_stream, void* stream)
   return static_cast<hipStream_t>(stream);
 }
 
+/* One copy of a *_sync call's round trip (sync_round_trip): `bytes` between host memory and buf + offset. */
+struct sync_copy {
+  dev_buffer* buf;
+  size_t      offset, bytes;
+  const void* from; /* host memory copied to the device before the stage runs, or null */
+  void*       to;   /* host memory the device's bytes are copied to after it, or null */
+};
+inline sync_copy to_device(dev_buffer& buf, size_t offset, const void* host, size_t bytes)
+{
+  return {&buf, offset, bytes, host, nullptr};
+}
+inline sync_copy to_host(dev_buffer& buf, size_t offset, void* host, size_t bytes)
+{
+  return {&buf, offset, bytes, nullptr, host};
+}
+
 } // namespace ldpc_hip
 
 struct ldpc_hip_plan;
@@ -177,7 +197,7 @@ struct ldpc_hip_ctx {
   ldpc_hip::desc_table    d_modsegs; /* ldpc_hip_modulate_launch segments */
   ldpc_hip::desc_table    d_rmmod;   /* ldpc_hip_rate_match_modulate_launch codeblocks */
   ldpc_hip::desc_table    d_eqsegs;  /* ldpc_hip_equalize_launch segments */
-  ldpc_hip::desc_table    d_precode; /* ldpc_hip_precode_map_launch / _sync: rows, mask words, weights */
+  ldpc_hip::desc_table    d_precode; /* ldpc_hip_precode_map_launch / _sync: make_precode_table's blob, as bytes */
   ldpc_hip::desc_table    d_tbaux;   /* ldpc_hip_tb_join_launch: its TB's descriptor, TB and chunk per workgroup */
   ldpc_hip::dev_buffer    d_tbwork;  /* ldpc_hip_tb_join_launch: per-TB chunk CRCs + arrival counter (zero at rest) */
   ldpc_hip::demod_tables  dtab{};    /* demodulator slopes / intercepts (make_demod_tables) */
@@ -256,6 +276,43 @@ struct ldpc_hip_ctx {
       e = launch(table.as<T>());
     }
     return e == hipSuccess ? LDPC_HIP_OK : hip_fail(e, what);
+  }
+  /* The host round trip of a stage's *_sync entry point, on the context's stream: every copy's scratch buffer reserved
+   * (one named more than once for its largest offset + bytes), the to_device copies queued, run() (the stage's segments
+   * on the scratch; a code other than LDPC_HIP_OK is returned as it is), the to_host copies queued, the stream
+   * synchronised. `name` is the stage's in the error of a HIP failure, which also says the step. */
+  template <typename Run>
+  int sync_round_trip(const char* name, std::initializer_list<ldpc_hip::sync_copy> copies, Run&& run)
+  {
+    hipError_t e = hipSuccess;
+    for (const ldpc_hip::sync_copy& c : copies) {
+      size_t need = 0;
+      for (const ldpc_hip::sync_copy& o : copies) {
+        need = o.buf == c.buf ? std::max(need, o.offset + o.bytes) : need;
+      }
+      if ((e = c.buf->reserve(need)) != hipSuccess) {
+        return hip_fail(e, std::string("hipMalloc(") + name + ")");
+      }
+    }
+    for (const ldpc_hip::sync_copy& c : copies) {
+      if (c.from != nullptr && (e = hipMemcpyAsync(c.buf->as<uint8_t>() + c.offset, c.from, c.bytes,
+                                                   hipMemcpyHostToDevice, stream)) != hipSuccess) {
+        return hip_fail(e, std::string("hipMemcpyAsync(") + name + " in)");
+      }
+    }
+    const int r = run();
+    if (r != LDPC_HIP_OK) {
+      return r;
+    }
+    for (const ldpc_hip::sync_copy& c : copies) {
+      if (c.to != nullptr && e == hipSuccess) {
+        e = hipMemcpyAsync(c.to, c.buf->as<uint8_t>() + c.offset, c.bytes, hipMemcpyDeviceToHost, stream);
+      }
+    }
+    if (e != hipSuccess || (e = hipStreamSynchronize(stream)) != hipSuccess) {
+      return hip_fail(e, std::string(name) + "_sync");
+    }
+    return LDPC_HIP_OK;
   }
 };
 

@@ -2,6 +2,10 @@
 #include "ldpc_hip_descs.h"
 
 #include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <utility>
 
 namespace ldpc_hip {
 
@@ -57,6 +61,10 @@ const char* add_blocks(uint64_t& blocks, uint64_t units, uint64_t per_block, con
   blocks += (units + per_block - 1U) / per_block;
   return blocks <= MAX_LAUNCH_BLOCKS ? nullptr : too_many;
 }
+
+/* A weight component the reference's complex multiply handles without its NaN fall-back (__mulsc3, taken only when
+ * both result components are NaN): finite and below 2^64, so that no intermediate overflows (127 2^64 2 4 < FLT_MAX). */
+bool weight_ok(float v) { return std::isfinite(v) && std::fabs(v) < 18446744073709551616.0F; }
 
 } // namespace
 
@@ -435,6 +443,97 @@ const char* make_eq_seg(const ldpc_hip_eq_desc& d, uint64_t& blocks, eq_seg& out
   out.nof_tx_layers = d.nof_tx_layers;
   return add_blocks(blocks, d.nof_re, static_cast<uint64_t>(EQ_BLOCK) * EQ_RES,
                     "equalize: too many REs for one launch");
+}
+
+/* ---- precoder ---- */
+const char* make_precode_table(uint32_t n, const ldpc_hip_precode_desc* descs, const float* weights,
+                               uint32_t nof_weights, const uint64_t* masks, uint32_t nof_mask_words, bool compact,
+                               uint64_t in_stride, precode_table& t)
+{
+  t = precode_table{};
+  for (uint64_t i = 0; i != 2ULL * nof_weights; ++i) {
+    if (!weight_ok(weights[i])) {
+      return "precode: a weight component is not finite or is 2^64 or more in magnitude";
+    }
+  }
+  /* a mask's words with their prefix counts, once per (first word, words) */
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> seen;
+  uint64_t                                          blocks = 0;
+  for (uint32_t i = 0; i != n; ++i) {
+    const ldpc_hip_precode_desc& d = descs[i];
+    if (!precode_supported(d.nof_layers, d.nof_ports)) {
+      return "precode: unsupported topology (1 <= layers <= ports <= 4)";
+    }
+    if (d.prg_size == 0) {
+      return "precode: prg_size must be at least 1";
+    }
+    if (!compact && d.width > d.port_stride) {
+      return "precode: a row is wider than its port stride";
+    }
+    const uint32_t nw = (d.width + 63U) / 64U;
+    if (d.mask_offset > nof_mask_words || nw > nof_mask_words - d.mask_offset) {
+      return "precode: a row's mask lies outside the masks";
+    }
+    const uint64_t* m = masks + d.mask_offset;
+    if (d.width % 64U != 0 && (m[nw - 1] >> (d.width % 64U)) != 0) {
+      return "precode: a mask bit beyond the row's width";
+    }
+    uint32_t lo = nw, hi = 0;
+    for (uint32_t w = 0; w != nw; ++w) {
+      if (m[w] != 0) {
+        lo = lo == nw ? w : lo;
+        hi = w;
+      }
+    }
+    if (lo == nw) {
+      continue; /* no masked RE */
+    }
+    const uint32_t prg_subc = compact ? 0xffffffffU : 12U * d.prg_size;
+    const uint32_t k_last   = hi * 64U + 63U - static_cast<uint32_t>(__builtin_clzll(m[hi]));
+    const uint64_t wl       = static_cast<uint64_t>(d.nof_layers) * d.nof_ports;
+    if (k_last / prg_subc >= d.nof_prg || d.weight_offset > nof_weights ||
+        d.nof_prg * wl > nof_weights - d.weight_offset) {
+      return "precode: a masked subcarrier's PRG lies outside the weight block";
+    }
+    auto it = seen.find({d.mask_offset, nw});
+    if (it == seen.end()) {
+      it = seen.emplace(std::make_pair(d.mask_offset, nw), static_cast<uint32_t>(t.words.size())).first;
+      uint64_t prefix = 0;
+      for (uint32_t w = 0; w != nw; ++w) {
+        t.words.push_back(precode_word{m[w], static_cast<uint32_t>(prefix), 0});
+        prefix += static_cast<uint64_t>(__builtin_popcountll(m[w]));
+      }
+    }
+    precode_row r{};
+    r.in_offset  = d.sym_offset;
+    r.in_stride  = in_stride;
+    r.out_offset = d.grid_offset;
+    r.out_stride = d.port_stride;
+    r.word0      = it->second;
+    r.weight0    = d.weight_offset;
+    r.k_begin    = lo * 64U;
+    r.k_end      = std::min(d.width, (hi + 1U) * 64U);
+    r.prg_subc   = prg_subc;
+    r.block0     = static_cast<uint32_t>(blocks);
+    r.nof_layers = d.nof_layers;
+    r.nof_ports  = d.nof_ports;
+    if (const char* why = add_blocks(blocks, r.k_end - r.k_begin, static_cast<uint64_t>(PC_BLOCK) * PC_RES,
+                                     "precode: too many blocks in one launch")) {
+      return why;
+    }
+    t.rows.push_back(r);
+  }
+  if (t.rows.empty()) {
+    return nullptr; /* nothing to launch: no blocks, an empty blob */
+  }
+  t.nblocks    = static_cast<uint32_t>(blocks);
+  t.words_at   = t.rows.size() * sizeof(precode_row);
+  t.weights_at = t.words_at + t.words.size() * sizeof(precode_word);
+  t.blob.resize(t.weights_at + 8U * static_cast<size_t>(nof_weights));
+  std::memcpy(t.blob.data(), t.rows.data(), t.words_at);
+  std::memcpy(t.blob.data() + t.words_at, t.words.data(), t.weights_at - t.words_at);
+  std::memcpy(t.blob.data() + t.weights_at, weights, 8U * static_cast<size_t>(nof_weights));
+  return nullptr;
 }
 
 } // namespace ldpc_hip

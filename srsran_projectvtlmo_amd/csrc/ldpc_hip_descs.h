@@ -1,8 +1,9 @@
 /*
  * The one translation of each C-ABI descriptor (include/srsran_ldpc_hip.h) into the work item the kernels read
- * (ldpc_hip_device.h, ldpc_equalize.h), with its validation, the segment launches' included. Host only: no HIP runtime
- * call, no context. Each make_* returns the reason its descriptor is invalid, or nullptr after filling the work item;
- * the entry points report the reason through ldpc_hip_last_error with LDPC_HIP_EINVAL.
+ * (ldpc_hip_device.h, ldpc_equalize.h, ldpc_precode.h), with its validation, the segment launches' and the precoder's
+ * table included. Host only: no HIP runtime call, no context. Each make_* returns the reason its descriptor is invalid,
+ * or nullptr after filling the work item; the entry points report the reason through ldpc_hip_last_error with
+ * LDPC_HIP_EINVAL.
  */
 #pragma once
 
@@ -11,6 +12,7 @@
 
 #include "ldpc_equalize.h"
 #include "ldpc_graph.h"
+#include "ldpc_precode.h"
 
 namespace ldpc_hip {
 
@@ -91,5 +93,26 @@ const char* make_segs(uint32_t n, const D* descs, std::vector<G>& segs, uint32_t
   nblocks = static_cast<uint32_t>(blocks);
   return nullptr;
 }
+
+/* ---- precoder ---- */
+/* a launch's table: rows, then mask words, then weights (16-byte aligned each), and the three as the launch uploads
+ * them: blob[0, words_at) the rows, [words_at, weights_at) the words, then 8 bytes per weight */
+struct precode_table {
+  std::vector<precode_row>  rows;
+  std::vector<precode_word> words;
+  uint32_t                  nblocks = 0;
+  std::vector<uint8_t>      blob;
+  size_t                    words_at = 0, weights_at = 0;
+};
+/* A launch's rows: the weights validated first, then every row in the caller's order (topology, prg_size, width against
+ * the port stride, the mask's words inside `masks`, no bit at or past the width, and, for a row with a masked RE, its
+ * last masked subcarrier's PRG and its weight block inside `weights`). A mask's words are stored once per (mask_offset,
+ * words) with the set bits before each; a row without a masked RE is dropped, one with works on [k_begin, k_end), its
+ * non-zero words, from block0. No row left: no blocks and an empty blob, whatever the weights.
+ * compact: the rows are a channel_precoder call's, one PRG whatever its length and no port-stride check; in_stride is
+ * every row's (the compact cf32 input's layer planes; the ci8 forms do not read it). */
+const char* make_precode_table(uint32_t n, const ldpc_hip_precode_desc* descs, const float* weights,
+                               uint32_t nof_weights, const uint64_t* masks, uint32_t nof_mask_words, bool compact,
+                               uint64_t in_stride, precode_table& t);
 
 } // namespace ldpc_hip

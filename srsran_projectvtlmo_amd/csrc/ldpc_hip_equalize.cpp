@@ -88,30 +88,17 @@ int ldpc_hip_equalize_sync(ldpc_hip_ctx* ctx, int algorithm, uint32_t nof_re, ui
   const size_t nsym = static_cast<size_t>(nof_re) * nof_rx_ports * 4U;
   const size_t nest = nsym * nof_tx_layers;
   const size_t nout = static_cast<size_t>(nof_re) * nof_tx_layers;
-  hipError_t   e;
   /* d_llr: received REs then estimates (nsym is a multiple of 4 bytes, so the estimates stay element-aligned) */
-  if ((e = ctx->d_llr.reserve(nsym + nest)) != hipSuccess || (e = ctx->d_sym.reserve(nout * 8U)) != hipSuccess ||
-      (e = ctx->d_nv.reserve(nout * 4U)) != hipSuccess) {
-    return ctx->hip_fail(e, "hipMalloc(equalize)");
-  }
-  uint8_t* in = ctx->d_llr.as<uint8_t>();
-  if ((e = hipMemcpyAsync(in, ch_symbols, nsym, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(in + nsym, ch_estimates, nest, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) {
-    return ctx->hip_fail(e, "hipMemcpyAsync(equalize in)");
-  }
-  const int r = equalize_segments(ctx, 1, &d, reinterpret_cast<const uint16_t*>(in),
-                                  reinterpret_cast<const uint16_t*>(in + nsym), ctx->d_sym.as<float>(),
-                                  ctx->d_nv.as<float>(), ctx->stream);
-  if (r != LDPC_HIP_OK) {
-    return r;
-  }
-  if ((e = hipMemcpyAsync(eq_symbols, ctx->d_sym.ptr, nout * 8U, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(eq_noise_vars, ctx->d_nv.ptr, nout * 4U, hipMemcpyDeviceToHost, ctx->stream)) !=
-          hipSuccess ||
-      (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
-    return ctx->hip_fail(e, "equalize_sync");
-  }
-  return LDPC_HIP_OK;
+  return ctx->sync_round_trip(
+      "equalize",
+      {to_device(ctx->d_llr, 0, ch_symbols, nsym), to_device(ctx->d_llr, nsym, ch_estimates, nest),
+       to_host(ctx->d_sym, 0, eq_symbols, nout * 8U), to_host(ctx->d_nv, 0, eq_noise_vars, nout * 4U)},
+      [&] {
+        const uint8_t* in = ctx->d_llr.as<uint8_t>();
+        return equalize_segments(ctx, 1, &d, reinterpret_cast<const uint16_t*>(in),
+                                 reinterpret_cast<const uint16_t*>(in + nsym), ctx->d_sym.as<float>(),
+                                 ctx->d_nv.as<float>(), ctx->stream);
+      });
 }
 
 } /* extern "C" */

@@ -82,25 +82,14 @@ int ldpc_hip_modulate_sync(ldpc_hip_ctx* ctx, uint32_t nof_symbols, int modulati
   (void)hipSetDevice(ctx->device);
   const size_t nin  = (static_cast<size_t>(nof_symbols) * bits_per_symbol(modulation) + 7U) / 8U;
   const size_t nout = static_cast<size_t>(nof_symbols) * (format == LDPC_HIP_SYM_CI8 ? 2U : 8U);
-  hipError_t   e;
-  if ((e = ctx->d_llr.reserve(nin)) != hipSuccess || (e = ctx->d_sym.reserve(nout)) != hipSuccess) {
-    return ctx->hip_fail(e, "hipMalloc(modulate)");
-  }
-  if ((e = hipMemcpyAsync(ctx->d_llr.ptr, bits, nin, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) {
-    return ctx->hip_fail(e, "hipMemcpyAsync(modulate in)");
-  }
   ldpc_hip_mod_desc d{};
   d.nof_symbols = nof_symbols;
   d.modulation  = static_cast<uint8_t>(modulation);
-  const int r   = modulate_segments(ctx, 1, &d, ctx->d_llr.as<uint8_t>(), ctx->d_sym.ptr, format, ctx->stream);
-  if (r != LDPC_HIP_OK) {
-    return r;
-  }
-  if ((e = hipMemcpyAsync(symbols, ctx->d_sym.ptr, nout, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
-      (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
-    return ctx->hip_fail(e, "modulate_sync");
-  }
-  return LDPC_HIP_OK;
+  return ctx->sync_round_trip("modulate", {to_device(ctx->d_llr, 0, bits, nin), to_host(ctx->d_sym, 0, symbols, nout)},
+                              [&] {
+                                return modulate_segments(ctx, 1, &d, ctx->d_llr.as<uint8_t>(), ctx->d_sym.ptr, format,
+                                                         ctx->stream);
+                              });
 }
 
 int ldpc_hip_rate_match_modulate_launch(ldpc_hip_ctx* ctx, uint32_t nof_cbs, const ldpc_hip_rm_desc* descs,

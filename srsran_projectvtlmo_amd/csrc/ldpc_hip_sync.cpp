@@ -358,32 +358,17 @@ int ldpc_hip_demodulate_sync(ldpc_hip_ctx* ctx, uint32_t nof_symbols, int modula
     return ctx->fail(LDPC_HIP_EINVAL, "demodulate_sync: null argument");
   }
   (void)hipSetDevice(ctx->device);
-  const size_t nllr = static_cast<size_t>(nof_symbols) * bits_per_symbol(modulation);
-  hipError_t   e;
-  if ((e = ctx->d_sym.reserve(static_cast<size_t>(nof_symbols) * 8)) != hipSuccess ||
-      (e = ctx->d_nv.reserve(static_cast<size_t>(nof_symbols) * 4)) != hipSuccess ||
-      (e = ctx->d_llr.reserve(nllr)) != hipSuccess) {
-    return ctx->hip_fail(e, "hipMalloc(demodulate)");
-  }
-  if ((e = hipMemcpyAsync(ctx->d_sym.ptr, symbols, static_cast<size_t>(nof_symbols) * 8, hipMemcpyHostToDevice,
-                          ctx->stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(ctx->d_nv.ptr, noise_vars, static_cast<size_t>(nof_symbols) * 4, hipMemcpyHostToDevice,
-                          ctx->stream)) != hipSuccess) {
-    return ctx->hip_fail(e, "hipMemcpyAsync(demodulate in)");
-  }
+  const size_t        n = nof_symbols;
   ldpc_hip_demod_desc d{};
   d.nof_symbols = nof_symbols;
   d.modulation  = static_cast<uint8_t>(modulation);
-  const int r   = demodulate_segments(ctx, 1, &d, ctx->d_sym.as<float>(), ctx->d_nv.as<float>(),
-                                      ctx->d_llr.as<int8_t>(), ctx->stream);
-  if (r != LDPC_HIP_OK) {
-    return r;
-  }
-  if ((e = hipMemcpyAsync(llrs, ctx->d_llr.ptr, nllr, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
-      (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
-    return ctx->hip_fail(e, "demodulate_sync");
-  }
-  return LDPC_HIP_OK;
+  return ctx->sync_round_trip("demodulate",
+                              {to_device(ctx->d_sym, 0, symbols, n * 8), to_device(ctx->d_nv, 0, noise_vars, n * 4),
+                               to_host(ctx->d_llr, 0, llrs, n * bits_per_symbol(modulation))},
+                              [&] {
+                                return demodulate_segments(ctx, 1, &d, ctx->d_sym.as<float>(), ctx->d_nv.as<float>(),
+                                                           ctx->d_llr.as<int8_t>(), ctx->stream);
+                              });
 }
 
 int ldpc_hip_descramble_sync(ldpc_hip_ctx* ctx, uint32_t c_init, uint64_t seq_offset, uint32_t n, const int8_t* in,
@@ -399,26 +384,14 @@ int ldpc_hip_descramble_sync(ldpc_hip_ctx* ctx, uint32_t c_init, uint64_t seq_of
     return ctx->fail(LDPC_HIP_EINVAL, "descramble_sync: null argument");
   }
   (void)hipSetDevice(ctx->device);
-  hipError_t e;
-  if ((e = ctx->d_llr.reserve(n)) != hipSuccess) {
-    return ctx->hip_fail(e, "hipMalloc(descramble)");
-  }
-  if ((e = hipMemcpyAsync(ctx->d_llr.ptr, in, n, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) {
-    return ctx->hip_fail(e, "hipMemcpyAsync(descramble in)");
-  }
   ldpc_hip_prs_seg d{};
   d.seq_offset = seq_offset;
   d.length     = n;
   d.c_init     = c_init;
-  const int r  = prs_segments(ctx, 1, &d, false, ctx->d_llr.as<uint8_t>(), ctx->d_llr.as<uint8_t>(), ctx->stream);
-  if (r != LDPC_HIP_OK) {
-    return r;
-  }
-  if ((e = hipMemcpyAsync(out, ctx->d_llr.ptr, n, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
-      (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
-    return ctx->hip_fail(e, "descramble_sync");
-  }
-  return LDPC_HIP_OK;
+  /* in place in d_llr */
+  return ctx->sync_round_trip("descramble", {to_device(ctx->d_llr, 0, in, n), to_host(ctx->d_llr, 0, out, n)}, [&] {
+    return prs_segments(ctx, 1, &d, false, ctx->d_llr.as<uint8_t>(), ctx->d_llr.as<uint8_t>(), ctx->stream);
+  });
 }
 
 } /* extern "C" */

@@ -19,6 +19,7 @@
  * 16-byte boundary of the symbol buffer leaves in 16-byte stores (8 ci8 or 2 cf32 symbols each; the four ci8 symbols of
  * a 256-QAM chunk in one 8-byte store); other segments and the last, partial chunk in element stores. No LDS.
  */
+#include "ldpc_block_item.h"
 #include "ldpc_hip_launch.h"
 #include "ldpc_prs_device.h"
 
@@ -149,22 +150,6 @@ __device__ __forceinline__ void mod_scramble(uint32_t (&W)[NW], uint32_t x1, uin
   }
 }
 
-/* this block's segment: the last one with block0 <= blockIdx.x (segments are in block order) */
-template <typename T, typename F>
-__device__ __forceinline__ uint32_t mod_find(const T* __restrict__ items, uint32_t n, F block0)
-{
-  uint32_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) / 2;
-    if (block0(items[mid]) <= blockIdx.x) {
-      lo = mid;
-    } else {
-      hi = mid;
-    }
-  }
-  return lo;
-}
-
 /* stand-alone: the chunk's bytes from the packed input, never past the segment's last byte */
 template <int MOD, bool CI8>
 __device__ __forceinline__ void mod_segment(const mod_seg& sg, uint32_t chunk, const uint8_t* __restrict__ bits_base,
@@ -261,7 +246,7 @@ __global__ void __launch_bounds__(MOD_BLOCK)
     ldpc_modulate_kernel(const mod_seg* __restrict__ segs, uint32_t nseg, const uint8_t* __restrict__ bits_base,
                          uint8_t* __restrict__ sym_base)
 {
-  const mod_seg  sg    = segs[mod_find(segs, nseg, [](const mod_seg& s) { return s.block0; })];
+  const mod_seg  sg    = segs[block_item(segs, nseg)];
   const uint32_t chunk = (blockIdx.x - sg.block0) * MOD_BLOCK + threadIdx.x;
   uint8_t*       out   = sym_base + sg.sym_offset * (CI8 ? 2U : 8U);
   const bool     vec   = (reinterpret_cast<uintptr_t>(out) & 15U) == 0;
@@ -280,7 +265,7 @@ __global__ void __launch_bounds__(MOD_BLOCK)
     ldpc_rate_match_modulate_kernel(const rm_mod_cb* __restrict__ cbs, uint32_t ncb,
                                     const uint8_t* __restrict__ cw_base, uint8_t* __restrict__ sym_base)
 {
-  const rm_mod_cb c     = cbs[mod_find(cbs, ncb, [](const rm_mod_cb& s) { return s.mod.block0; })];
+  const rm_mod_cb c     = cbs[block_item(cbs, ncb, [](const rm_mod_cb& s) { return s.mod.block0; })];
   const uint32_t  chunk = (blockIdx.x - c.mod.block0) * MOD_BLOCK + threadIdx.x;
   uint8_t*        out   = sym_base + c.mod.sym_offset * (CI8 ? 2U : 8U);
   const bool      vec   = (reinterpret_cast<uintptr_t>(out) & 15U) == 0;

@@ -1,7 +1,7 @@
 /*
  * The precoder's work item and host launcher (downlink, behind the modulation mapper), shared by its kernel unit
- * (ldpc_precode_kernels.hip) and its host unit (ldpc_hip_precode.cpp). Nothing of the decoder, the uplink family, the
- * mapper or the equalizer is declared here.
+ * (ldpc_precode_kernels.hip), its translation (ldpc_hip_descs.cpp) and its host unit (ldpc_hip_precode.cpp). Nothing
+ * of the decoder, the uplink family, the mapper or the equalizer is declared here.
  */
 #pragma once
 

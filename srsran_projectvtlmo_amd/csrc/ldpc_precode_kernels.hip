@@ -23,6 +23,7 @@
  *
  * The ten (L, P) bodies sit behind one block-uniform switch (a row is block-uniform), as the equalizer's.
  */
+#include "ldpc_block_item.h"
 #include "ldpc_precode.h"
 
 #pragma clang fp contract(off)
@@ -231,17 +232,7 @@ __global__ void __launch_bounds__(PC_BLOCK)
     ldpc_precode_kernel(const precode_row* __restrict__ rows, uint32_t nrows, const precode_word* __restrict__ words,
                         const float* __restrict__ weights, const void* __restrict__ in, void* __restrict__ out)
 {
-  /* this block's row: the last one with block0 <= blockIdx.x (rows are in block order) */
-  uint32_t lo = 0, hi = nrows;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) / 2;
-    if (rows[mid].block0 <= blockIdx.x) {
-      lo = mid;
-    } else {
-      hi = mid;
-    }
-  }
-  const precode_row rw = rows[lo];
+  const precode_row rw = rows[block_item(rows, nrows)];
   const uint32_t    k0 = rw.k_begin + ((blockIdx.x - rw.block0) * PC_BLOCK + threadIdx.x) * PC_RES;
   /* block-uniform; the host admits these ten only */
 #define PC_CASE(L, P)                                                          \

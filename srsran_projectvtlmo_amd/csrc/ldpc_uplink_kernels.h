@@ -6,6 +6,7 @@
  */
 #pragma once
 
+#include "ldpc_block_item.h"
 #include "ldpc_dematch_body.h"
 #include "ldpc_device_util.h"
 #include "ldpc_diag.h"
@@ -344,17 +345,7 @@ __global__ void __launch_bounds__(DEMOD_BLOCK)
   if (threadIdx.x < NW) {
     reinterpret_cast<uint32_t*>(&s_tab)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&tab)[threadIdx.x];
   }
-  /* segment of this block: the last one with block0 <= blockIdx.x (segments are in block order) */
-  uint32_t lo = 0, hi = nseg;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) / 2;
-    if (segs[mid].block0 <= blockIdx.x) {
-      lo = mid;
-    } else {
-      hi = mid;
-    }
-  }
-  const demod_seg sg = segs[lo];
+  const demod_seg sg = segs[block_item(segs, nseg)];
   __syncthreads();
   const uint32_t i = (blockIdx.x - sg.block0) * DEMOD_BLOCK + threadIdx.x;
   if (i >= sg.nof_symbols) {
@@ -392,16 +383,7 @@ template <bool BITS>
 __global__ void __launch_bounds__(PRS_BLOCK)
     ldpc_prs_kernel(const prs_seg* __restrict__ segs, uint32_t nseg, const uint8_t* in_base, uint8_t* out_base)
 {
-  uint32_t lo = 0, hi = nseg; /* this block's segment: the last one with block0 <= blockIdx.x */
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) / 2;
-    if (segs[mid].block0 <= blockIdx.x) {
-      lo = mid;
-    } else {
-      hi = mid;
-    }
-  }
-  const prs_seg  sg = segs[lo];
+  const prs_seg  sg = segs[block_item(segs, nseg)];
   const uint32_t nw = sg.length / 32U + (sg.length % 32U != 0U ? 1U : 0U);
   const uint32_t w0 = ((blockIdx.x - sg.block0) * PRS_BLOCK + threadIdx.x) * PRS_WORDS;
   if (w0 >= nw) {

@@ -72,6 +72,14 @@ static const char* const R_EQ_SCALING  = "equalize: tx_scaling must be positive"
 static const char* const R_EQ_STRIDE   = "equalize: a plane stride below nof_re";
 static const char* const R_EQ_SEG      = "equalize: a segment holds fewer than 2^31 outputs";
 static const char* const R_EQ_MANY     = "equalize: too many REs for one launch";
+/* the precoder's, as ldpc_hip_precode.cpp gave them before its translation moved into the descriptor unit */
+static const char* const R_PC_WEIGHT   = "precode: a weight component is not finite or is 2^64 or more in magnitude";
+static const char* const R_PC_TOPOLOGY = "precode: unsupported topology (1 <= layers <= ports <= 4)";
+static const char* const R_PC_PRG      = "precode: prg_size must be at least 1";
+static const char* const R_PC_STRIDE   = "precode: a row is wider than its port stride";
+static const char* const R_PC_MASK     = "precode: a row's mask lies outside the masks";
+static const char* const R_PC_TAIL     = "precode: a mask bit beyond the row's width";
+static const char* const R_PC_REACH    = "precode: a masked subcarrier's PRG lies outside the weight block";
 
 static ldpc_hip_dec_desc dec_desc(int bg, unsigned Z)
 {
@@ -783,6 +791,314 @@ static void test_equalizer()
                                             R_EQ_MANY, make_eq_segs);
 }
 
+static ldpc_hip_precode_desc pc_desc(uint32_t width, uint32_t mask_offset, unsigned layers, unsigned ports,
+                                     uint32_t nof_prg, unsigned prg_size)
+{
+  ldpc_hip_precode_desc d{};
+  d.sym_offset    = 5;
+  d.grid_offset   = 9;
+  d.port_stride   = width + 3U;
+  d.mask_offset   = mask_offset;
+  d.weight_offset = 0;
+  d.nof_prg       = nof_prg;
+  d.width         = width;
+  d.prg_size      = static_cast<uint16_t>(prg_size);
+  d.nof_layers    = static_cast<uint8_t>(layers);
+  d.nof_ports     = static_cast<uint8_t>(ports);
+  return d;
+}
+
+/* ceil(width / 64) mask words with bits [lo, hi) set */
+static std::vector<uint64_t> pc_mask(uint32_t width, uint32_t lo, uint32_t hi)
+{
+  std::vector<uint64_t> m((width + 63U) / 64U, 0);
+  for (uint32_t k = lo; k < hi; ++k) {
+    m[k / 64U] |= 1ULL << (k % 64U);
+  }
+  return m;
+}
+
+static std::vector<float> pc_weights(uint32_t nof_weights)
+{
+  std::vector<float> w(2U * nof_weights);
+  for (size_t i = 0; i != w.size(); ++i) {
+    w[i] = 0.25f * static_cast<float>(i % 7U) - 0.5f;
+  }
+  return w;
+}
+
+static float float_of(uint32_t bits)
+{
+  float f;
+  std::memcpy(&f, &bits, sizeof(f));
+  return f;
+}
+
+struct pc_launch {
+  std::vector<ldpc_hip_precode_desc> descs;
+  std::vector<float>                 weights;
+  std::vector<uint64_t>              masks;
+  bool                               compact   = false;
+  uint64_t                           in_stride = 0;
+  const char* make(precode_table& t) const
+  {
+    return make_precode_table(static_cast<uint32_t>(descs.size()), descs.data(), weights.data(),
+                              static_cast<uint32_t>(weights.size() / 2U), masks.data(),
+                              static_cast<uint32_t>(masks.size()), compact, in_stride, t);
+  }
+};
+
+/* An accepted launch's table against the plain rule: per row the first and last non-zero mask word give k_begin and
+ * k_end, ceil((k_end - k_begin) / (PC_BLOCK PC_RES)) its blocks; a mask's words once per (mask_offset, words), each
+ * with the popcount of the row's earlier words; the blob the three arrays back to back. */
+static void check_pc_table(const pc_launch& l, int line)
+{
+  precode_table t;
+  t.blob.assign(3, 0xa5); /* a used table is reset */
+  t.nblocks = 77;
+  const char* why = l.make(t);
+  if (why != nullptr) {
+    std::printf("FAIL line %d: refused: %s\n", line, why);
+    ++g_failed;
+    return;
+  }
+  std::vector<precode_row>  rows;
+  std::vector<precode_word> words;
+  struct shared {
+    uint32_t mask_offset, nw, word0;
+  };
+  std::vector<shared> seen;
+  uint32_t            blocks = 0;
+  for (const ldpc_hip_precode_desc& d : l.descs) {
+    const uint32_t  nw = (d.width + 63U) / 64U;
+    const uint64_t* m  = l.masks.data() + d.mask_offset;
+    int             first = -1, last = -1;
+    for (uint32_t w = 0; w != nw; ++w) {
+      if (m[w] != 0) {
+        first = first < 0 ? static_cast<int>(w) : first;
+        last  = static_cast<int>(w);
+      }
+    }
+    if (first < 0) {
+      continue;
+    }
+    uint32_t word0 = static_cast<uint32_t>(words.size());
+    bool     found = false;
+    for (const shared& s : seen) {
+      if (s.mask_offset == d.mask_offset && s.nw == nw) {
+        word0 = s.word0;
+        found = true;
+      }
+    }
+    if (!found) {
+      seen.push_back({d.mask_offset, nw, word0});
+      uint32_t prefix = 0;
+      for (uint32_t w = 0; w != nw; ++w) {
+        words.push_back(precode_word{m[w], prefix, 0});
+        for (uint64_t b = m[w]; b != 0; b &= b - 1U) {
+          ++prefix;
+        }
+      }
+    }
+    precode_row r{};
+    r.in_offset  = d.sym_offset;
+    r.in_stride  = l.in_stride;
+    r.out_offset = d.grid_offset;
+    r.out_stride = d.port_stride;
+    r.word0      = word0;
+    r.weight0    = d.weight_offset;
+    r.k_begin    = static_cast<uint32_t>(first) * 64U;
+    r.k_end      = std::min(d.width, (static_cast<uint32_t>(last) + 1U) * 64U);
+    r.prg_subc   = l.compact ? 0xffffffffU : 12U * d.prg_size;
+    r.block0     = blocks;
+    r.nof_layers = d.nof_layers;
+    r.nof_ports  = d.nof_ports;
+    blocks += (r.k_end - r.k_begin + PC_BLOCK * PC_RES - 1U) / (PC_BLOCK * PC_RES);
+    rows.push_back(r);
+  }
+  bool ok = t.rows.size() == rows.size() && t.words.size() == words.size() && t.nblocks == blocks;
+  for (size_t i = 0; ok && i != rows.size(); ++i) {
+    const precode_row &a = t.rows[i], &b = rows[i];
+    ok = a.in_offset == b.in_offset && a.in_stride == b.in_stride && a.out_offset == b.out_offset &&
+         a.out_stride == b.out_stride && a.word0 == b.word0 && a.weight0 == b.weight0 && a.k_begin == b.k_begin &&
+         a.k_end == b.k_end && a.prg_subc == b.prg_subc && a.block0 == b.block0 && a.nof_layers == b.nof_layers &&
+         a.nof_ports == b.nof_ports && std::all_of(a.pad, a.pad + 6, [](uint8_t p) { return p == 0; });
+  }
+  for (size_t i = 0; ok && i != words.size(); ++i) {
+    ok = t.words[i].bits == words[i].bits && t.words[i].prefix == words[i].prefix && t.words[i].pad == 0;
+  }
+  if (ok && rows.empty()) {
+    ok = t.blob.empty();
+  } else if (ok) {
+    const size_t nwb = 4U * l.weights.size();
+    ok = t.words_at == 64U * rows.size() && t.weights_at == t.words_at + 16U * words.size() &&
+         t.blob.size() == t.weights_at + nwb && std::memcmp(t.blob.data(), t.rows.data(), t.words_at) == 0 &&
+         std::memcmp(t.blob.data() + t.words_at, t.words.data(), 16U * words.size()) == 0 &&
+         std::memcmp(t.blob.data() + t.weights_at, l.weights.data(), nwb) == 0;
+  }
+  if (!ok) {
+    std::printf("FAIL line %d: the precoder's table differs from the plain rule\n", line);
+    ++g_failed;
+  }
+}
+#define CHECK_PC_TABLE(l) check_pc_table(l, __LINE__)
+
+/* "precode: too many blocks in one launch" is not tested: 2^31 blocks of 256 subcarriers need gigabytes of masks. */
+static void test_precoder()
+{
+  precode_table t;
+  /* a: PRBs 1 to 4 of an 11-PRB row, PRGs 0 and 1 of size 4, 2 layers on 4 ports */
+  pc_launch a;
+  a.descs   = {pc_desc(132, 0, 2, 4, 2, 4)};
+  a.weights = pc_weights(16);
+  a.masks   = pc_mask(132, 12, 60);
+  CHECK_PC_TABLE(a);
+  CHECK(a.make(t) == nullptr && t.rows.size() == 1 && t.words.size() == 3 && t.nblocks == 1);
+  CHECK(t.words[0].prefix == 0 && t.words[1].prefix == 48 && t.words[2].prefix == 48);
+  CHECK(t.rows[0].k_begin == 0 && t.rows[0].k_end == 64 && t.rows[0].block0 == 0 && t.rows[0].prg_subc == 48);
+  CHECK(t.rows[0].in_offset == 5 && t.rows[0].in_stride == 0 && t.rows[0].out_offset == 9);
+  CHECK(t.rows[0].out_stride == 135 && t.rows[0].weight0 == 0 && t.rows[0].nof_layers == 2 && t.rows[0].nof_ports == 4);
+  CHECK(t.words_at == 64 && t.weights_at == 64 + 48 && t.blob.size() == 64 + 48 + 128);
+  /* b: the last PRB of a 273-PRB row is one block high in the grid */
+  pc_launch b;
+  b.descs   = {pc_desc(3276, 0, 1, 1, 69, 4)};
+  b.weights = pc_weights(69);
+  b.masks   = pc_mask(3276, 3264, 3276);
+  CHECK_PC_TABLE(b);
+  CHECK(b.make(t) == nullptr && t.words.size() == 52 && t.nblocks == 1 && t.words[51].prefix == 0);
+  CHECK(t.rows[0].k_begin == 3264 && t.rows[0].k_end == 3276);
+  /* c: the whole row */
+  pc_launch c = b;
+  c.masks     = pc_mask(3276, 0, 3276);
+  CHECK_PC_TABLE(c);
+  CHECK(c.make(t) == nullptr && t.nblocks == 13 && t.rows[0].k_begin == 0 && t.rows[0].k_end == 3276);
+  CHECK(t.words[51].prefix == 51 * 64);
+  /* d: two rows of one mask share its words; another mask's come behind them */
+  pc_launch d = a;
+  d.descs     = {pc_desc(132, 0, 2, 4, 2, 4), pc_desc(132, 0, 1, 2, 3, 4), pc_desc(132, 3, 2, 4, 2, 4)};
+  d.descs[1].sym_offset = 1000, d.descs[1].weight_offset = 4;
+  const std::vector<uint64_t> other = pc_mask(132, 70, 96);
+  d.masks.insert(d.masks.end(), other.begin(), other.end());
+  CHECK_PC_TABLE(d);
+  CHECK(d.make(t) == nullptr && t.rows.size() == 3 && t.words.size() == 6 && t.nblocks == 3);
+  CHECK(t.rows[0].word0 == 0 && t.rows[1].word0 == 0 && t.rows[2].word0 == 3 && t.rows[1].weight0 == 4);
+  CHECK(t.rows[2].k_begin == 64 && t.rows[2].k_end == 128 && t.rows[2].block0 == 2);
+  /* e: a row without a masked RE is dropped, and the next row's block0 continues the count */
+  pc_launch e = c;
+  e.descs     = {c.descs[0], pc_desc(3276, 52, 1, 1, 69, 4), c.descs[0]};
+  e.masks.resize(2U * 52U, 0);
+  e.descs[2].grid_offset = 1U << 20;
+  CHECK_PC_TABLE(e);
+  CHECK(e.make(t) == nullptr && t.rows.size() == 2 && t.nblocks == 26 && t.rows[1].block0 == 13);
+  CHECK(t.rows[1].out_offset == (1U << 20) && t.rows[1].word0 == 0 && t.words.size() == 52);
+  /* f: no masked RE at all: nothing to launch, whatever the weights' reach */
+  pc_launch f = d;
+  std::fill(f.masks.begin(), f.masks.end(), 0);
+  f.descs[0].nof_prg = 1000, f.descs[1].weight_offset = 999999, f.descs[2].nof_prg = 0;
+  CHECK_PC_TABLE(f);
+  CHECK(f.make(t) == nullptr && t.rows.empty() && t.words.empty() && t.nblocks == 0 && t.blob.empty());
+  /* g: a width of whole words has no tail to check; the last bit is the last subcarrier */
+  pc_launch g;
+  g.descs   = {pc_desc(64, 0, 1, 1, 2, 4)};
+  g.weights = pc_weights(2);
+  g.masks   = pc_mask(64, 63, 64);
+  CHECK_PC_TABLE(g);
+  CHECK(g.make(t) == nullptr && t.rows[0].k_begin == 0 && t.rows[0].k_end == 64 && t.nblocks == 1);
+  g.descs[0].nof_prg = 1; /* subcarrier 63 is PRG 1 */
+  REASON(g.make(t), R_PC_REACH);
+  /* h: the compact form is one PRG whatever its length, and carries the in_stride it was given */
+  pc_launch h;
+  h.descs     = {pc_desc(300, 0, 2, 2, 1, 1)};
+  h.weights   = pc_weights(4);
+  h.masks     = pc_mask(300, 0, 300);
+  h.compact   = true;
+  h.in_stride = 777;
+  CHECK_PC_TABLE(h);
+  CHECK(h.make(t) == nullptr && t.rows[0].prg_subc == 0xffffffffU && t.rows[0].in_stride == 777 && t.nblocks == 2);
+  h.descs[0].port_stride = 299; /* no port-stride check in the compact form */
+  CHECK_PC_TABLE(h);
+  h.compact = false;
+  REASON(h.make(t), R_PC_STRIDE);
+
+  /* weights: the largest float below 2^64 passes; 2^64, the infinities and NaN do not, as either component */
+  for (const size_t at : {size_t{14}, size_t{15}}) {
+    pc_launch w   = a;
+    w.weights[at] = float_of(0x5F7FFFFFU);
+    CHECK_PC_TABLE(w);
+    w.weights[at] = -float_of(0x5F7FFFFFU);
+    CHECK_PC_TABLE(w);
+    for (const uint32_t bits : {0x5F800000U, 0xDF800000U, 0x7F800000U, 0xFF800000U, 0x7FC00000U}) {
+      w.weights[at] = float_of(bits);
+      REASON(w.make(t), R_PC_WEIGHT);
+    }
+  }
+
+  /* one rejection per reason */
+  const unsigned outside[][2] = {{0, 1}, {1, 0}, {2, 1}, {3, 2}, {4, 3}, {1, 5}, {5, 5}, {0, 0}};
+  for (const auto& lp : outside) {
+    pc_launch x           = a;
+    x.descs[0].nof_layers = static_cast<uint8_t>(lp[0]);
+    x.descs[0].nof_ports  = static_cast<uint8_t>(lp[1]);
+    REASON(x.make(t), R_PC_TOPOLOGY);
+  }
+  pc_launch x = a;
+  x.descs[0].prg_size = 0;
+  REASON(x.make(t), R_PC_PRG);
+  x = a, x.descs[0].port_stride = 131;
+  REASON(x.make(t), R_PC_STRIDE);
+  x = a, x.descs[0].mask_offset = 4; /* past the three words; nothing of the masks is read */
+  REASON(x.make(t), R_PC_MASK);
+  x = a, x.descs[0].mask_offset = 0xffffffffU;
+  REASON(x.make(t), R_PC_MASK);
+  x = a, x.descs[0].mask_offset = 1; /* three words from word 1 of three */
+  REASON(x.make(t), R_PC_MASK);
+  x = a, x.masks.pop_back();
+  REASON(x.make(t), R_PC_MASK);
+  x = a, x.descs[0].width = 59, x.descs[0].nof_prg = 2; /* bit 59 is the first past a width of 59 */
+  REASON(x.make(t), R_PC_TAIL);
+  x.descs[0].width = 60;
+  CHECK_PC_TABLE(x);
+  x = a, x.descs[0].nof_prg = 1; /* subcarrier 48 is PRG 1 */
+  REASON(x.make(t), R_PC_REACH);
+  x = a, x.descs[0].weight_offset = 17; /* past the 16 weights */
+  REASON(x.make(t), R_PC_REACH);
+  x = a, x.descs[0].weight_offset = 1; /* the block's end past them */
+  REASON(x.make(t), R_PC_REACH);
+  x = a, x.weights.resize(30);
+  REASON(x.make(t), R_PC_REACH);
+  /* nof_prg x layers x ports is a 64-bit product: 2^29 x 8 and (2^32 - 1) x 8 do not wrap into the array */
+  x = a, x.descs[0].nof_prg = 0xffffffffU;
+  REASON(x.make(t), R_PC_REACH);
+  x.descs[0].nof_prg = 0x20000000U;
+  REASON(x.make(t), R_PC_REACH);
+
+  /* order: the weights; then row by row topology, prg_size, width against the stride, the mask's range, its tail,
+   * and the PRG / weight reach */
+  x = a;
+  x.descs[0].nof_prg = 1, x.descs[0].width = 50;
+  REASON(x.make(t), R_PC_TAIL);
+  x.masks.pop_back(), x.masks.pop_back(), x.masks.pop_back(); /* width 50 is one word: none left */
+  REASON(x.make(t), R_PC_MASK);
+  x.descs[0].port_stride = 49;
+  REASON(x.make(t), R_PC_STRIDE);
+  x.descs[0].prg_size = 0;
+  REASON(x.make(t), R_PC_PRG);
+  x.descs[0].nof_ports = 1;
+  REASON(x.make(t), R_PC_TOPOLOGY);
+  x.weights[3] = float_of(0x7FC00000U);
+  REASON(x.make(t), R_PC_WEIGHT);
+  /* the first invalid row in the caller's order decides; a refused weight comes before every row, used or not */
+  x = d, x.descs[1].nof_prg = 0, x.descs[2].nof_layers = 5;
+  REASON(x.make(t), R_PC_REACH);
+  x.descs[0].prg_size = 0;
+  REASON(x.make(t), R_PC_PRG);
+  x = f, x.weights.back() = float_of(0x7F800000U);
+  REASON(x.make(t), R_PC_WEIGHT);
+  /* no row and no weight: accepted, nothing produced */
+  CHECK(make_precode_table(0, nullptr, nullptr, 0, nullptr, 0, false, 0, t) == nullptr && t.rows.empty() &&
+        t.blob.empty() && t.nblocks == 0);
+}
+
 int main()
 {
   CHECK(align16(0) == 0 && align16(1) == 16 && align16(16) == 16 && align16(17) == 32);
@@ -806,6 +1122,7 @@ int main()
   test_mapper();
   test_rate_match_mapper();
   test_equalizer();
+  test_precoder();
   std::printf(g_failed == 0 ? "test_descs: all passed\n" : "test_descs: %d checks failed\n", g_failed);
   return g_failed == 0 ? 0 : 1;
 }
