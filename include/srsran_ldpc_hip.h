@@ -563,6 +563,64 @@ int ldpc_hip_precode_map_launch(ldpc_hip_ctx* ctx, uint32_t nof_rows, const ldpc
 int ldpc_hip_precode_sync(ldpc_hip_ctx* ctx, uint32_t nof_re, uint32_t nof_layers, uint32_t nof_ports,
                           const void* input, int input_format, const float* weights, float* output);
 
+/* ---- PDSCH DM-RS: generation and mapping into the resource grid -----------------------------------------------
+ * dmrs_pdsch_processor::map (include/srsran/phy/upper/signal_processors/dmrs_pdsch_processor.h,
+ * dmrs_pdsch_processor_impl.cpp:84-262) over dmrs_helper.h:44-109, pseudo_random_generator_impl.cpp:154-246 and
+ * resource_grid_mapper_impl::map(const re_buffer_reader&, ...) (resource_grid_mapper_impl.cpp:47-147, 165-291): on DM-RS
+ * symbol l the sequence of c_init = ((14 slot_index + l + 1) (2 scrambling_id + 1) 2^17 + 2 scrambling_id + n_scid)
+ * mod 2^31; pilot j of resource block n (dpr = 6 pilots per RB and CDM group for type 1, 4 for type 2) from the bits
+ * b = 2 (dpr (n - reference_point_k_rb) + j) and b + 1 as (a ^ c(b) << 31, a ^ c(b + 1) << 31) on the bits of
+ * a = (float)(M_SQRT1_2 * (double)amplitude); DM-RS port i is layer i in CDM group i / 2 on subcarriers 2 j + g (type
+ * 1) or {2 g, 2 g + 1, 6 + 2 g, 7 + 2 g} (type 2) of the RB, the odd-j pilots of an odd port negated; per CDM group the
+ * precoder's arithmetic on its one or two layers (sum = x_0 w_0, sum += x_1 w_1, uncontracted float32) and its cbf16
+ * rounding; one layer on one port with the weight 1 + 0j stores the pilots unmultiplied, as the reference's mapper.
+ * The grid REs are the reference's bit for bit (built without its SIMD loops). DM-RS types 1 and 2 at every
+ * 1 <= layers <= ports <= 4, one PRG: one weight matrix [port][layer] per transmission (the reference asserts on more).
+ * An amplitude of 2^56 or more in magnitude is outside the contract and not checked. */
+/* Host only: 1 for type 1 or 2 at the ten topologies, else 0. */
+int ldpc_hip_dmrs_pdsch_supported(uint32_t type, uint32_t nof_layers, uint32_t nof_ports);
+/* Host only: c_init of DM-RS symbol `symbol`, on the exact integer (the reference's 32-bit wrap gives the same). */
+uint32_t ldpc_hip_dmrs_pdsch_c_init(uint32_t slot_index, uint32_t symbol, uint32_t scrambling_id, uint32_t n_scid);
+/* One transmission (dmrs_pdsch_processor::config_t). Resource block n is allocated when bit n % 64 of word
+ * mask_offset + n / 64 of `rb_masks` is set; DM-RS symbol l of it writes, per port p, the element
+ * grid_offset + p port_stride + l symbol_stride + k for the subcarriers k of its pilots. */
+typedef struct {                 /* 64 bytes */
+  uint64_t grid_offset;          /* port 0, symbol 0, subcarrier 0 of the transmission, in elements from d_grid       */
+  uint64_t symbol_stride;        /* elements between OFDM symbols, >= width                                           */
+  uint64_t port_stride;          /* elements between ports, >= (last DM-RS symbol) symbol_stride + width              */
+  uint32_t mask_offset;          /* the RB mask's first word in rb_masks; ceil(nof_rb / 64) words, none past nof_rb   */
+  uint32_t weight_offset;        /* the weights [port][layer], in cf32 elements from weights                          */
+  uint32_t nof_rb;               /* resource blocks of the RB mask                                                    */
+  uint32_t width;                /* subcarriers of a grid row, >= 12 nof_rb                                           */
+  uint32_t slot_index;           /* slot_point::slot_index()                                                          */
+  uint32_t scrambling_id;        /* <= 65535                                                                          */
+  uint32_t reference_point_k_rb; /* no allocated RB below it                                                          */
+  float    amplitude;
+  uint16_t symbols_mask;         /* bit l: OFDM symbol l carries DM-RS; not 0, no bit at or above 14                  */
+  uint8_t  type;                 /* 1 or 2                                                                            */
+  uint8_t  nof_layers, nof_ports;
+  uint8_t  n_scid;               /* 0 or 1                                                                            */
+  uint8_t  pad[2];
+} ldpc_hip_dmrs_pdsch_desc;
+/* Generates and maps the DM-RS of nof_descs transmissions on a device grid in one launch, asynchronously on `stream`
+ * (NULL = the context stream). descs, weights (nof_weights cf32 elements, float re, im) and rb_masks (nof_mask_words
+ * words) are host arrays; they are uploaded into a per-context table of this launch's own (not the precoder's: both
+ * launches may sit in one captured graph), which an equal call on the same stream reuses (so: launch once, then
+ * capture). output_format LDPC_HIP_SYM_CBF16: d_grid holds cbf16 elements (4 bytes, aligned to 4);
+ * LDPC_HIP_SYM_CF32: cf32 elements (8 bytes, aligned to 8) of the same geometry counted in elements, the values before
+ * the bf16 rounding. No grid byte outside a transmission's DM-RS REs on its first nof_ports ports is written;
+ * transmissions of different types and topologies may share a launch; one with an empty RB mask is skipped. Two
+ * transmissions that overlap in the grid are the caller's error and are not detected. LDPC_HIP_EINVAL (nothing is
+ * launched): a type other than 1 or 2, a topology outside the ten, a weight or amplitude that is not finite or a
+ * weight component of 2^64 or more in magnitude, an empty symbols_mask or a bit of it at or above 14, an allocated RB
+ * below reference_point_k_rb, 12 nof_rb above width, width above symbol_stride, the last DM-RS symbol's row past
+ * port_stride, an RB mask or weight matrix outside its array or a mask bit at or past nof_rb, scrambling_id above
+ * 65535, n_scid above 1, an output_format that is neither, a null argument. */
+#define LDPC_HIP_SYM_CBF16 2  /* bf16 re, bf16 im (cbf16_t), a resource grid's element */
+int ldpc_hip_dmrs_pdsch_map_launch(ldpc_hip_ctx* ctx, uint32_t nof_descs, const ldpc_hip_dmrs_pdsch_desc* descs,
+                                   const float* weights, uint32_t nof_weights, const uint64_t* rb_masks,
+                                   uint32_t nof_mask_words, void* d_grid, int output_format, void* stream);
+
 /* ---- launch graphs: one submission per slot ---------------------------------------------------------------- */
 /* srsRAN runs the PUSCH decode chain once per slot with the same shape slot after slot (pusch_decoder_impl /
  * pusch_decoder_hw_impl call the decoder per codeblock and join per TB). Here the chain's *_launch calls on `stream`

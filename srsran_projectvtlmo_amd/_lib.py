@@ -44,8 +44,9 @@ EXPORTED_SYMBOLS = [
     "ldpc_hip_rate_match_modulate_launch",
     "ldpc_hip_equalize_supported", "ldpc_hip_equalize_launch", "ldpc_hip_equalize_sync",
     "ldpc_hip_precode_supported", "ldpc_hip_precode_map_launch", "ldpc_hip_precode_sync",
+    "ldpc_hip_dmrs_pdsch_supported", "ldpc_hip_dmrs_pdsch_c_init", "ldpc_hip_dmrs_pdsch_map_launch",
 ]
-SYM_CF32, SYM_CI8 = 0, 1   # LDPC_HIP_SYM_*
+SYM_CF32, SYM_CI8, SYM_CBF16 = 0, 1, 2   # LDPC_HIP_SYM_*
 EQ_ZF, EQ_MMSE = 0, 1      # LDPC_HIP_EQ_*
 HARQ_STRIDE = 25344   # LDPC_HIP_HARQ_STRIDE
 
@@ -186,6 +187,19 @@ class PrecodeDesc(ctypes.Structure):
 assert ctypes.sizeof(PrecodeDesc) == 48
 
 
+class DmrsPdschDesc(ctypes.Structure):
+    """ldpc_hip_dmrs_pdsch_desc (include/srsran_ldpc_hip.h)."""
+    _fields_ = [("grid_offset", ctypes.c_uint64), ("symbol_stride", ctypes.c_uint64), ("port_stride", ctypes.c_uint64),
+                ("mask_offset", ctypes.c_uint32), ("weight_offset", ctypes.c_uint32), ("nof_rb", ctypes.c_uint32),
+                ("width", ctypes.c_uint32), ("slot_index", ctypes.c_uint32), ("scrambling_id", ctypes.c_uint32),
+                ("reference_point_k_rb", ctypes.c_uint32), ("amplitude", ctypes.c_float),
+                ("symbols_mask", ctypes.c_uint16), ("type", ctypes.c_uint8), ("nof_layers", ctypes.c_uint8),
+                ("nof_ports", ctypes.c_uint8), ("n_scid", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 2)]
+
+
+assert ctypes.sizeof(DmrsPdschDesc) == 64
+
+
 class TbResult(ctypes.Structure):
     _fields_ = [("tb_crc_ok", ctypes.c_uint8), ("written", ctypes.c_uint8), ("nof_cbs_ok", ctypes.c_uint16)]
 
@@ -272,6 +286,9 @@ def load():
         "ldpc_hip_precode_supported": (I, [U32, U32]),
         "ldpc_hip_precode_map_launch": (I, [P, U32, ctypes.POINTER(PrecodeDesc), P, U32, P, U32, P, P, P]),
         "ldpc_hip_precode_sync": (I, [P, U32, U32, U32, P, I, P, P]),
+        "ldpc_hip_dmrs_pdsch_supported": (I, [U32, U32, U32]),
+        "ldpc_hip_dmrs_pdsch_c_init": (U32, [U32, U32, U32, U32]),
+        "ldpc_hip_dmrs_pdsch_map_launch": (I, [P, U32, ctypes.POINTER(DmrsPdschDesc), P, U32, P, U32, P, I, P]),
         "ldpc_hip_capture_begin": (I, [P, P]),
         "ldpc_hip_capture_end": (I, [P, P, ctypes.POINTER(P)]),
         "ldpc_hip_graph_launch": (I, [P, P]),

@@ -1,8 +1,8 @@
 /*
  * The segment launches' block lookup on the device: a launch's work items lie in block order, each with the launch's
  * block count before it (block0, ldpc_hip_descs.h), and a workgroup finds its own by blockIdx.x. Shared by the kernels
- * of the demodulator, the sequence generator, the modulation mapper, the equalizer and the precoder; nothing of the
- * decoder or of any of these stages is declared here.
+ * of the demodulator, the sequence generator, the modulation mapper, the equalizer, the precoder and the DM-RS
+ * generator; nothing of the decoder or of any of these stages is declared here.
  */
 #pragma once
 

@@ -19,6 +19,7 @@ static_assert(sizeof(ldpc_hip_tb_result) == 4, "ldpc_hip_tb_result layout");
 static_assert(sizeof(ldpc_hip_enc_desc) == 24, "ldpc_hip_enc_desc layout");
 static_assert(sizeof(ldpc_hip_rm_desc) == 32, "ldpc_hip_rm_desc layout");
 static_assert(sizeof(ldpc_hip_demod_desc) == 32, "ldpc_hip_demod_desc layout");
+static_assert(sizeof(ldpc_hip_dmrs_pdsch_desc) == 64, "ldpc_hip_dmrs_pdsch_desc layout");
 
 namespace {
 
@@ -532,6 +533,138 @@ const char* make_precode_table(uint32_t n, const ldpc_hip_precode_desc* descs, c
   t.blob.resize(t.weights_at + 8U * static_cast<size_t>(nof_weights));
   std::memcpy(t.blob.data(), t.rows.data(), t.words_at);
   std::memcpy(t.blob.data() + t.words_at, t.words.data(), t.weights_at - t.words_at);
+  std::memcpy(t.blob.data() + t.weights_at, weights, 8U * static_cast<size_t>(nof_weights));
+  return nullptr;
+}
+
+/* ---- PDSCH DM-RS ---- */
+uint32_t dmrs_c_init(uint32_t slot_index, uint32_t symbol, uint32_t scrambling_id, uint32_t n_scid)
+{
+  /* 2^17 times the low 14 bits of the first product is that term modulo 2^31; nothing here can wrap 64 bits for a
+   * scrambling_id of 16 bits */
+  const uint64_t first = (14ULL * slot_index + symbol + 1ULL) * (2ULL * scrambling_id + 1ULL);
+  return static_cast<uint32_t>((((first & 0x3fffULL) << 17) + 2ULL * scrambling_id + n_scid) & PRS_MASK);
+}
+
+const char* make_dmrs_table(uint32_t n, const ldpc_hip_dmrs_pdsch_desc* descs, const float* weights,
+                            uint32_t nof_weights, const uint64_t* rb_masks, uint32_t nof_mask_words, dmrs_table& t)
+{
+  t = dmrs_table{};
+  for (uint64_t i = 0; i != 2ULL * nof_weights; ++i) {
+    if (!weight_ok(weights[i])) {
+      return "dmrs_pdsch: a weight component is not finite or is 2^64 or more in magnitude";
+    }
+  }
+  /* a mask's words once per (first word, words) */
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> seen;
+  std::vector<uint64_t>                             words;
+  uint64_t                                          blocks = 0;
+  for (uint32_t i = 0; i != n; ++i) {
+    const ldpc_hip_dmrs_pdsch_desc& d = descs[i];
+    if (d.type != 1 && d.type != 2) {
+      return "dmrs_pdsch: the DM-RS type is 1 or 2";
+    }
+    if (!dmrs_supported(d.type, d.nof_layers, d.nof_ports)) {
+      return "dmrs_pdsch: unsupported topology (1 <= layers <= ports <= 4)";
+    }
+    if (!std::isfinite(d.amplitude)) {
+      return "dmrs_pdsch: the amplitude is not finite";
+    }
+    if (d.scrambling_id > 65535U) {
+      return "dmrs_pdsch: scrambling_id above 65535";
+    }
+    if (d.n_scid > 1U) {
+      return "dmrs_pdsch: n_scid above 1";
+    }
+    if (d.symbols_mask == 0) {
+      return "dmrs_pdsch: an empty symbol mask";
+    }
+    if ((d.symbols_mask >> DMRS_NSYMB) != 0) {
+      return "dmrs_pdsch: a symbol-mask bit at or above 14";
+    }
+    if (12ULL * d.nof_rb > d.width) {
+      return "dmrs_pdsch: 12 nof_rb above the row's width";
+    }
+    if (d.width > d.symbol_stride) {
+      return "dmrs_pdsch: a row is wider than its symbol stride";
+    }
+    const uint32_t l_last = 31U - static_cast<uint32_t>(__builtin_clz(d.symbols_mask));
+    /* (a symbol stride whose 14 symbols would wrap 64 bits is above every port stride) */
+    if (d.symbol_stride > (~0ULL - d.width) / DMRS_NSYMB || l_last * d.symbol_stride + d.width > d.port_stride) {
+      return "dmrs_pdsch: the DM-RS symbols are wider than the port stride";
+    }
+    const uint32_t nw = (d.nof_rb + 63U) / 64U;
+    if (d.mask_offset > nof_mask_words || nw > nof_mask_words - d.mask_offset) {
+      return "dmrs_pdsch: an RB mask lies outside the masks";
+    }
+    const uint64_t* m = rb_masks + d.mask_offset;
+    if (d.nof_rb % 64U != 0 && (m[nw - 1] >> (d.nof_rb % 64U)) != 0) {
+      return "dmrs_pdsch: an RB-mask bit beyond nof_rb";
+    }
+    if (d.weight_offset > nof_weights ||
+        static_cast<uint32_t>(d.nof_layers) * d.nof_ports > nof_weights - d.weight_offset) {
+      return "dmrs_pdsch: a weight matrix lies outside the weights";
+    }
+    uint32_t lo = nw, hi = 0;
+    for (uint32_t w = 0; w != nw; ++w) {
+      if (m[w] != 0) {
+        lo = lo == nw ? w : lo;
+        hi = w;
+      }
+    }
+    if (lo == nw) {
+      continue; /* no allocated RB */
+    }
+    const uint32_t rb_begin = lo * 64U + static_cast<uint32_t>(__builtin_ctzll(m[lo]));
+    const uint32_t rb_end   = hi * 64U + 64U - static_cast<uint32_t>(__builtin_clzll(m[hi]));
+    if (rb_begin < d.reference_point_k_rb) {
+      return "dmrs_pdsch: an allocated RB below reference_point_k_rb";
+    }
+    auto it = seen.find({d.mask_offset, nw});
+    if (it == seen.end()) {
+      it = seen.emplace(std::make_pair(d.mask_offset, nw), static_cast<uint32_t>(words.size())).first;
+      words.insert(words.end(), m, m + nw);
+    }
+    const float* w00 = weights + 2ULL * d.weight_offset;
+    dmrs_row     r{};
+    r.out_stride = d.port_stride;
+    /* dmrs_pdsch_processor_impl.cpp:89: M_SQRT1_2 times the amplitude in double, rounded once */
+    r.a          = static_cast<float>(0.70710678118654752440 * static_cast<double>(d.amplitude));
+    r.word0      = it->second;
+    r.weight0    = d.weight_offset;
+    r.rb_begin   = rb_begin;
+    r.rb_end     = rb_end;
+    r.ref_rb     = d.reference_point_k_rb;
+    r.type       = d.type;
+    r.nof_layers = d.nof_layers;
+    r.nof_ports  = d.nof_ports;
+    /* resource_grid_mapper_impl.cpp:94-95, 230-231: cf_t == 1.0F, so an imaginary part of -0 passes too */
+    r.bypass = d.nof_layers == 1 && d.nof_ports == 1 && w00[0] == 1.0F && w00[1] == 0.0F ? 1 : 0;
+    for (uint32_t l = 0; l != DMRS_NSYMB; ++l) {
+      if (((d.symbols_mask >> l) & 1U) == 0) {
+        continue;
+      }
+      const ldpc_hip_prs_state st = prs_state_at(dmrs_c_init(d.slot_index, l, d.scrambling_id, d.n_scid), 0);
+      r.out_offset                = d.grid_offset + l * d.symbol_stride;
+      r.x1                        = st.x1;
+      r.x2                        = st.x2;
+      r.block0                    = static_cast<uint32_t>(blocks);
+      if (const char* why = add_blocks(blocks, rb_end - rb_begin, static_cast<uint64_t>(DMRS_BLOCK) * DMRS_RBS,
+                                       "dmrs_pdsch: too many blocks in one launch")) {
+        return why;
+      }
+      t.rows.push_back(r);
+    }
+  }
+  if (t.rows.empty()) {
+    return nullptr; /* nothing to launch: no blocks, an empty blob */
+  }
+  t.nblocks    = static_cast<uint32_t>(blocks);
+  t.words_at   = t.rows.size() * sizeof(dmrs_row);
+  t.weights_at = t.words_at + words.size() * sizeof(uint64_t);
+  t.blob.resize(t.weights_at + 8U * static_cast<size_t>(nof_weights));
+  std::memcpy(t.blob.data(), t.rows.data(), t.words_at);
+  std::memcpy(t.blob.data() + t.words_at, words.data(), t.weights_at - t.words_at);
   std::memcpy(t.blob.data() + t.weights_at, weights, 8U * static_cast<size_t>(nof_weights));
   return nullptr;
 }

@@ -1,15 +1,16 @@
 /*
  * The one translation of each C-ABI descriptor (include/srsran_ldpc_hip.h) into the work item the kernels read
- * (ldpc_hip_device.h, ldpc_equalize.h, ldpc_precode.h), with its validation, the segment launches' and the precoder's
- * table included. Host only: no HIP runtime call, no context. Each make_* returns the reason its descriptor is invalid,
- * or nullptr after filling the work item; the entry points report the reason through ldpc_hip_last_error with
- * LDPC_HIP_EINVAL.
+ * (ldpc_hip_device.h, ldpc_equalize.h, ldpc_precode.h, ldpc_dmrs.h), with its validation, the segment launches' and the
+ * precoder's and the DM-RS generator's tables included. Host only: no HIP runtime call, no context. Each make_* returns
+ * the reason its descriptor is invalid, or nullptr after filling the work item; the entry points report the reason
+ * through ldpc_hip_last_error with LDPC_HIP_EINVAL.
  */
 #pragma once
 
 #include <cstdint>
 #include <vector>
 
+#include "ldpc_dmrs.h"
 #include "ldpc_equalize.h"
 #include "ldpc_graph.h"
 #include "ldpc_precode.h"
@@ -114,5 +115,25 @@ struct precode_table {
 const char* make_precode_table(uint32_t n, const ldpc_hip_precode_desc* descs, const float* weights,
                                uint32_t nof_weights, const uint64_t* masks, uint32_t nof_mask_words, bool compact,
                                uint64_t in_stride, precode_table& t);
+
+/* ---- PDSCH DM-RS ---- */
+/* c_init of a DM-RS symbol (dmrs_pdsch_processor_impl.cpp:98), on the exact integer */
+uint32_t dmrs_c_init(uint32_t slot_index, uint32_t symbol, uint32_t scrambling_id, uint32_t n_scid);
+/* a launch's table: rows, then RB-mask words, then weights, and the three as the launch uploads them: blob[0, words_at)
+ * the rows, [words_at, weights_at) the words (8 bytes each), then 8 bytes per weight */
+struct dmrs_table {
+  std::vector<dmrs_row> rows;
+  uint32_t              nblocks = 0;
+  std::vector<uint8_t>  blob;
+  size_t                words_at = 0, weights_at = 0;
+};
+/* A launch's rows: the weights validated first, then every transmission in the caller's order (type and topology,
+ * amplitude, scrambling_id and n_scid, the symbol mask, 12 nof_rb against the width, the width against the symbol
+ * stride and the last DM-RS symbol's row against the port stride, the RB mask's words inside `rb_masks` with no bit at
+ * or past nof_rb, no allocated RB below the reference point, the weight matrix inside `weights`). A transmission with
+ * an empty RB mask is dropped; one with a set RB becomes one row per DM-RS symbol, on its lowest to its highest set
+ * RB, from block0. No row left: no blocks and an empty blob. */
+const char* make_dmrs_table(uint32_t n, const ldpc_hip_dmrs_pdsch_desc* descs, const float* weights,
+                            uint32_t nof_weights, const uint64_t* rb_masks, uint32_t nof_mask_words, dmrs_table& t);
 
 } // namespace ldpc_hip

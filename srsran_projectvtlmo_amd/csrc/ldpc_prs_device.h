@@ -1,7 +1,8 @@
 /*
  * The pseudo-random sequence on the device (TS 38.211 5.2.1; ldpc_hip_device.h "pseudo-random sequence generator"),
  * shared by the uplink (descrambler, packed-bit scrambler, the dematcher's fused descrambler: ldpc_dematch_body.h,
- * ldpc_uplink_kernels.h) and the downlink (the modulation mapper's scrambler: ldpc_modulation_kernels.hip).
+ * ldpc_uplink_kernels.h) and the downlink (the modulation mapper's scrambler: ldpc_modulation_kernels.hip; the PDSCH
+ * DM-RS generator: ldpc_dmrs_kernels.hip).
  * A thread owns a run of consecutive 32-bit sequence words of its segment: it jumps from the segment's start state to
  * its first word (prs_jump_words: one polynomial jump per non-zero radix-32 digit of the word index, the polynomials
  * from g_prs_jump, 1.5 KiB of constant data built at compile time from the recurrences) and then steps word by word
