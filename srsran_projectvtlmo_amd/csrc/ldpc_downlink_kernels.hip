@@ -420,6 +420,9 @@ __device__ __forceinline__ void pdsch_rate_match(const ratematch_cb& d, enc_lds&
     __syncthreads();
     const uint32_t nbc = min(nb - c0 / 8, static_cast<uint32_t>(ENC_OBUF));
     uint8_t*       dst = out + c0 / 8;
+    /* a destination off the 16-byte grid leaves in bytes only (n16 = 0). The encoder queue aligns every codeblock's
+     * output to 16 bytes and a chunk is 4096 bytes, so that path is not reached through it and no test runs it; a last
+     * chunk shorter than 16 bytes also has n16 = 0 and is tested (tests/rm_grid.py, row e_65576) */
     const uint32_t n16 = (reinterpret_cast<uintptr_t>(dst) & 15U) == 0 ? nbc / 16 : 0U;
     for (uint32_t k = threadIdx.x; k < n16; k += ENC_THREADS) {
       reinterpret_cast<uint4*>(dst)[k] = L.obuf[k];

@@ -107,11 +107,11 @@ def allot_trace(bg, Z, E, rv, Qm, F, Nref, new_data) -> set:
     return got
 
 
-def _up(E, Qm):
+def up(E, Qm):
     return (E + Qm - 1) // Qm * Qm
 
 
-def _qm_dividing(E, Qm):
+def qm_dividing(E, Qm):
     """Qm, or the next smaller modulation order that divides E (for rows whose length is meant exactly)."""
     return next(q for q in reversed(QMS) if q <= Qm and E % q == 0)
 
@@ -155,8 +155,8 @@ def branch_rows(bg, Z):
     out = []
     for name, Qm, rv, F, Nref, E, exact in rows:
         if exact:
-            Qm = _qm_dividing(E, Qm)
-        out.append((name, Qm, rv, F, Nref, _up(E, Qm)))
+            Qm = qm_dividing(E, Qm)
+        out.append((name, Qm, rv, F, Nref, up(E, Qm)))
     return out
 
 

@@ -1,5 +1,5 @@
-"""Records tests/golden/ref_*.npz and ref_dematch_grid.json (digests only) from the compiled reference
-(oracle/_ref/libsrsran_ref.so, `make -C oracle ref`).
+"""Records tests/golden/ref_*.npz, ref_dematch_grid.json and ref_rate_match_grid.json (digests only) from the compiled
+reference (oracle/_ref/libsrsran_ref.so, `make -C oracle ref`).
 
     python tests/golden/make_reference_fixtures.py
 
@@ -58,9 +58,24 @@ def record_dematch_grid():
     print(f"{path.name}: {len(cases)} cases, {path.stat().st_size} bytes")
 
 
+def record_rate_match_grid():
+    """tests/golden/ref_rate_match_grid.json: per row of tests/rm_grid.py the reference takes (all but the 'division'
+    rows) its numbers and the SHA-256 of the packed output the reference wrote for the oracle encoder's codeword."""
+    import json
+    from tests.rm_grid import reference_rows
+    cases = reference_rows()
+    doc = {"keys": list(C.RM_GRID_KEYS), "cases": [[c[k] for k in C.RM_GRID_KEYS] for c in cases],
+           "sha256": [C.rm_grid_digest(ref, c) for c in cases]}
+    path = C.GOLDEN / "ref_rate_match_grid.json"
+    path.write_text(json.dumps(doc, separators=(",", ":")) + "\n")
+    assert path.stat().st_size <= MAX_BYTES, f"{path.name}: {path.stat().st_size} bytes"
+    print(f"{path.name}: {len(cases)} cases, {path.stat().st_size} bytes")
+
+
 def main():
     assert ref.available(), "build oracle/_ref first: make -C oracle ref"
     record_dematch_grid()
+    record_rate_match_grid()
     for op, cases in (("decode", C.fixture_decode_cases()), ("decode_sf", C.fixture_decode_sf_cases()),
                       ("dematch", C.fixture_dematch_cases()), ("chain", C.chain_cases()),
                       ("demod", C.demod_cases(257)), ("descramble", C.descramble_cases()),

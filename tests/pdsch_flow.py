@@ -25,15 +25,26 @@ def tb_crc_value(tb_bits: np.ndarray) -> tuple[int, int]:
     return L, O.crc_bits(O.CRC16 if L == 16 else O.CRC24A, tb_bits)
 
 
-def cb_messages(tb_bits: np.ndarray, metas) -> np.ndarray:
-    """(C, K Z) message bits with the oracle's FILLER_BIT at the filler positions."""
-    m0 = metas[0]
-    C, Z, F, bg = m0.nof_cbs, m0.lifting_size, m0.nof_filler_bits, m0.base_graph
+def cb_messages(tb_bits: np.ndarray, metas=None, *, bg=None, Z=None, seg_bits=None, C=None, F=None,
+                tb_crc_bits=None) -> np.ndarray:
+    """(C, K Z) message bits with the oracle's FILLER_BIT at the filler positions. From `metas` (the segmenter's), or
+    from bg, Z, seg_bits (S, the data bits per segment), C, F given explicitly (and tb_crc_bits, 16 or 24): segment r
+    is bits [r S, (r + 1) S) of TB + TB CRC, zero-padded where the TB ends inside it or before it (a segment past the
+    end is all zero), then its CRC24B over those S bits when C > 1 (O.crc_bits: zero for an all-zero segment), then F
+    fillers; C = 1 has no codeblock CRC."""
+    if metas is not None:
+        m0 = metas[0]
+        C, Z, F, bg = m0.nof_cbs, m0.lifting_size, m0.nof_filler_bits, m0.base_graph
     KZ = O.BG_K[bg] * Z
     L, crc = tb_crc_value(tb_bits)
+    if tb_crc_bits is not None and tb_crc_bits != L:
+        L, crc = tb_crc_bits, O.crc_bits(O.CRC16 if tb_crc_bits == 16 else O.CRC24A, tb_bits)
     b = np.concatenate([tb_bits, np.array([(crc >> (L - 1 - i)) & 1 for i in range(L)], np.uint8)])
     cbc = 24 if C > 1 else 0
     kd = KZ - F - cbc
+    if metas is None:
+        assert seg_bits == kd, "nof_segment_bits + 24 + F == K Z"
+        assert kd * C >= b.size, "S C >= B"
     msgs = np.zeros((C, KZ), np.uint8)
     for r in range(C):
         seg = b[r * kd:(r + 1) * kd]
@@ -43,6 +54,76 @@ def cb_messages(tb_bits: np.ndarray, metas) -> np.ndarray:
             msgs[r, kd:kd + 24] = [(c >> (23 - i)) & 1 for i in range(24)]
         msgs[r, KZ - F:] = O.FILLER_BIT
     return msgs
+
+
+QM_NAME = {1: "BPSK", 2: "QPSK", 4: "QAM16", 6: "QAM64", 8: "QAM256"}
+ENC_ZERO_COPY_MAX_BYTES = 1024 * 1024   # csrc/ldpc_hip_enc_queue.cpp: above it a batch is copied around its launch
+ENC_DWQ_MAX_CBS = 8                     # and only a zero-copy batch of at most this many goes to the work queue
+
+
+def cb_staged_bytes(c) -> int:
+    """What one CB-mode codeblock adds to msg_used + out_used of the encoder queue (ldpc_hip_enc_queue::stage and
+    add_unit): its message bytes and 8 zero bytes, and its packed output, each rounded up to 16."""
+    def up16(n):
+        return (n + 15) // 16 * 16
+    return up16((O.BG_K[c["bg"]] * c["Z"] - c["F"] + 7) // 8 + 8) + up16((c["E"] + 7) // 8)
+
+
+def plan_batches(rows, max_cbs, max_bytes=None):
+    """The batches encode_cbs makes of `rows`, as [(first, end)]: rows in order, a batch closed when it holds max_cbs
+    codeblocks (the queue's max_queue_cbs, 0: 162) or when the next row would take its staged bytes above max_bytes."""
+    out, first, used = [], 0, 0
+    for i, c in enumerate(rows):
+        n = cb_staged_bytes(c)
+        assert max_bytes is None or n <= max_bytes, "one codeblock above the byte limit"
+        if i > first and (i - first == (max_cbs or 162) or (max_bytes is not None and used + n > max_bytes)):
+            out.append((first, i))
+            first, used = i, 0
+        used += n
+    return out + ([(first, len(rows))] if rows else [])
+
+
+def encode_cbs(enc, rows, messages, max_batch_bytes=None):
+    """CB mode with a configuration of its own per codeblock (ldpc_hip_enc_configure takes bg, Z, rm_length, Qm, rv,
+    Nref, F per codeblock, whatever TB they would come from), in pdsch_encoder_hw_impl::encode's call order: reserve ->
+    configure + enqueue until enqueue_operation returns False -> dequeue what was enqueued -> repeat -> free. With
+    max_batch_bytes the caller also stops enqueueing before the row that would take the batch's staged bytes
+    (cb_staged_bytes) above it, so that the queue keeps the batch on its zero-copy routes. rows: dicts with bg, Z, E,
+    rv, Qm, Nref, F; messages: their K Z message bits (fillers FILLER_BIT at the tail). Returns ([(one bit per byte,
+    packed)] per row, call counts and stats['batches'] = [(first row, end row, staged bytes)]); both arrays start as
+    0xEE."""
+    enc.reserve_queue()
+    out = [None] * len(rows)
+    stats = {"enqueue_false": 0, "dequeue_false": 0, "batches": []}
+    done = 0
+    while done < len(rows):
+        last, used = done, 0
+        for i in range(done, len(rows)):
+            c = rows[i]
+            n = cb_staged_bytes(c)
+            if max_batch_bytes is not None and i > done and used + n > max_batch_bytes:
+                break
+            KZ = O.BG_K[c["bg"]] * c["Z"]
+            cfg = hal.hw_pdsch_encoder_configuration(
+                base_graph_index=c["bg"], modulation=QM_NAME[c["Qm"]], nof_segments=1, rv=c["rv"],
+                lifting_size=c["Z"], Ncb=O.BG_N_SHORT[c["bg"]] * c["Z"], Nref=c["Nref"], nof_filler_bits=c["F"],
+                rm_length=c["E"], cb_mode=True)
+            enc.configure_operation(cfg, i - done)
+            if not enc.enqueue_operation(np.packbits(messages[i][:KZ - c["F"]]), None, i - done):
+                stats["enqueue_false"] += 1
+                break
+            last, used = i + 1, used + n
+        assert last > done, "an empty batch refused its first codeblock"
+        stats["batches"].append((done, last, used))
+        for i in range(done, last):
+            E = rows[i]["E"]
+            block, packed = np.full(E, 0xEE, np.uint8), np.full((E + 7) // 8, 0xEE, np.uint8)
+            while not enc.dequeue_operation(block, packed, i - done):
+                stats["dequeue_false"] += 1
+            out[i] = (block, packed)
+        done = last
+    enc.free_queue()
+    return out, stats
 
 
 def expected_codeword(tb_bytes: np.ndarray, bg: int, nof_ch_symbols: int, mod: str, nof_layers: int, rv: int,

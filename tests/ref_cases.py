@@ -365,9 +365,21 @@ def rate_match_cases(full=True):
     return cases
 
 
+def rm_message(c):
+    """A grid case's message (tests/rm_grid.py): K Z seeded bits, the oracle's FILLER_BIT at the last F positions."""
+    KZ = O.BG_K[c["bg"]] * c["Z"]
+    msg = sm_bits(c["seed"], KZ)
+    if c["F"]:
+        msg[KZ - c["F"]:] = O.FILLER_BIT
+    return msg
+
+
 def rate_match_input(c):
     """A codeblock's worth of random bits with the filler positions marked (the rate matcher does not look at whether
-    they form a codeword, so no encoder is involved)."""
+    they form a codeword, so no encoder is involved). A case of tests/rm_grid.py (it names its row) gets the oracle
+    encoder's codeword of rm_message instead: the fused encoder route can be given nothing else."""
+    if "row" in c:
+        return O.ldpc_encode(c["bg"], c["Z"], rm_message(c))
     N = O.BG_N_SHORT[c["bg"]] * c["Z"]
     cw = sm_bits(c["seed"], N)
     k = (O.BG_K[c["bg"]] - 2) * c["Z"]
@@ -377,6 +389,28 @@ def rate_match_input(c):
 
 def run_rate_match(impl, c, cw):
     return {"bits": np.packbits(impl.rate_match(cw, c["E"], c["rv"], c["Qm"], c["Nref"], c["bg"], c["Z"]))}
+
+
+def live_rate_match_cases():
+    """The differential test's rate matcher cases: rate_match_cases(), then every row of tests/rm_grid.py the reference
+    takes (the branch grid, every lifted graph, the staging rows without the 'division' ones)."""
+    from tests.rm_grid import reference_rows
+    return rate_match_cases() + reference_rows()
+
+
+def rm_grid_digest(impl, c, cw=None) -> str:
+    """SHA-256 of a grid case's packed output (tests/golden/ref_rate_match_grid.json records the reference's)."""
+    return digest(run_rate_match(impl, c, rate_match_input(c) if cw is None else cw)["bits"])
+
+
+RM_GRID_KEYS = ("bg", "Z", "E", "rv", "Qm", "Nref", "F", "seed", "row", "kind")
+
+
+def load_rm_grid():
+    """[(case, recorded digest)] of tests/golden/ref_rate_match_grid.json: case numbers and digests only."""
+    d = json.loads((Path(__file__).resolve().parent / "golden" / "ref_rate_match_grid.json").read_text())
+    assert d["keys"] == list(RM_GRID_KEYS)
+    return [(dict(zip(d["keys"], row)), sha) for row, sha in zip(d["cases"], d["sha256"])]
 
 
 # ---- CRC --------------------------------------------------------------------------------------------------------------

@@ -138,3 +138,105 @@ def test_pdsch_encoder_small_batches_both_routes(case, cb_mode, route):
         c.close()
     assert stats["enqueue_false"] == 0
     np.testing.assert_array_equal(got, expected_codeword(tb, bg, nsym, mod, layers, rv, Nref))
+
+
+# ---- TB mode: the message edges of enc_build -----------------------------------------------------------------------
+# ldpc_hip_enc_configure takes any TB-mode configuration with nof_segment_bits + 24 + F == K Z (C > 1) and S C >= B, so
+# these are built directly, not through the segmenter. In TB mode the device reads segment r at bit r S of TB + TB CRC
+# (byte r S / 8, bit offset r S % 8), zero-pads it to S bits, and attaches its CRC24B at bit S: word S / 32, shift
+# S % 32, spilling into the next word for a shift above 8; the CRC runs over ceil(S / 32) front-padded words, one per
+# thread and round of 256.
+# (name, bg, Z, S, C, TB bits, TB CRC bits)
+TB_EDGE_CASES = [
+    # C = 8 segments of an odd length: they start at all eight bit offsets
+    ("bit_offsets_bg2_z36", 2, 36, 335, 8, 8 * 335 - 16, 16),
+    ("bit_offsets_bg1_z104", 1, 104, 2263, 8, 8 * 2263 - 24, 24),
+] + [
+    # the CRC's place in its word: S % 32 = 0, below 8, at 8, above (the spill), up to 31
+    (f"crc_at_{S % 32}", 2, 36, S, 2, (2 * S - 16) // 8 * 8, 16) for S in (288, 289, 295, 296, 297, 312, 313, 319)
+] + [
+    ("crc_one_word_s20", 2, 6, 20, 2, 24, 16),            # CRC over at most 32 bits: one front-padded word
+    ("crc_one_word_s32", 2, 6, 32, 2, 48, 16),
+    ("crc_two_rounds", 1, 384, 8424, 2, 2 * 8424 - 24, 24),   # 264 CRC words: more than one per thread
+    ("short_last_segment", 2, 36, 300, 3, 656, 24),       # B = 680: the last segment holds 80 of 300 bits
+    ("segment_past_the_end", 2, 36, 300, 4, 656, 24),     # and a fourth one holds none
+    ("segment_starts_at_the_end", 2, 36, 300, 3, 576, 24),    # B = 600 = 2 S: the third starts where the TB ends
+]
+
+
+def _tb_edge_expected(bg, Z, S, C, tb_bits, L, Qm, rv, Ea, Eb, nshort):
+    import oracle as O
+    from tests.pdsch_flow import cb_messages
+    KZ = O.BG_K[bg] * Z
+    F = KZ - 24 - S
+    msgs = cb_messages(tb_bits, bg=bg, Z=Z, seg_bits=S, C=C, F=F, tb_crc_bits=L)
+    # cb_messages' slicing and CRC placement, restated from the TB's bits: segment r is bits [r S, r S + n) of TB + TB
+    # CRC and zeros up to S, its CRC24B (the packed-bytes routine, not the one cb_messages calls) sits at [S, S + 24)
+    tcrc = O.crc_bits(O.CRC16 if L == 16 else O.CRC24A, tb_bits)
+    b = np.concatenate([tb_bits, [(tcrc >> (L - 1 - i)) & 1 for i in range(L)]]).astype(np.uint8)
+    B = b.size
+    for r in range(C):
+        n = max(0, min(S, B - r * S))
+        seg = np.zeros(S, np.uint8)
+        seg[:n] = b[r * S:r * S + n]
+        assert np.array_equal(msgs[r, :S], seg)
+        crc = O.crc_packed(O.CRC24B, np.packbits(seg), S)
+        assert np.array_equal(msgs[r, S:S + 24], [(crc >> (23 - i)) & 1 for i in range(24)])
+        assert np.all(msgs[r, KZ - F:] == O.FILLER_BIT)
+        if n == 0:
+            assert crc == 0 and not np.any(msgs[r, :KZ - F])    # a segment past the end: all zero, zero CRC
+    return [O.rate_match(O.ldpc_encode(bg, Z, msgs[r]), Ea if r < nshort else Eb, rv, Qm, 0, bg, Z) for r in range(C)]
+
+
+@pytest.mark.parametrize("route", ["work_queue", "launch"])
+@pytest.mark.parametrize("case", TB_EDGE_CASES, ids=[c[0] for c in TB_EDGE_CASES])
+def test_pdsch_encoder_tb_mode_message_edges(case, route):
+    import oracle as O
+    from srsran_projectvtlmo_amd import _lib, hal
+    name, bg, Z, S, C, tbs, L = case
+    k = [c[0] for c in TB_EDGE_CASES].index(name)
+    KZ, N = O.BG_K[bg] * Z, O.BG_N_SHORT[bg] * Z
+    F = KZ - 24 - S
+    B = tbs + L
+    assert tbs % 8 == 0 and 0 <= F < (O.BG_K[bg] - 2) * Z and S * C >= B
+    if name.startswith("bit_offsets"):
+        assert {(r * S) % 8 for r in range(C)} == set(range(8)) and B == S * C
+    segs = [max(0, min(S, B - r * S)) for r in range(C)]
+    assert any(0 < n < S for n in segs) or not ("short" in name or "past" in name)
+    assert ("past" in name or "starts_at" in name) == (0 in segs)
+    rng = np.random.default_rng(500 + k)
+    tb = _tb(rng, tbs)
+    tb_bits = np.unpackbits(tb)
+    Qm, mod, rv = (2, "QPSK", k % 4) if k % 2 else (6, "QAM64", k % 4)
+    Ea = (N // 2 + 7 * k) // Qm * Qm
+    Eb, nshort = Ea + Qm, C // 2
+    want = _tb_edge_expected(bg, Z, S, C, tb_bits, L, Qm, rv, Ea, Eb, nshort)
+    crc = O.crc_bits(O.CRC16 if L == 16 else O.CRC24A, tb_bits)
+    cfg = hal.hw_pdsch_encoder_configuration(
+        nof_tb_bits=tbs, nof_tb_crc_bits=L, base_graph_index=bg, modulation=mod, nof_segments=C,
+        nof_short_segments=nshort, rv=rv, cw_length_a=Ea, cw_length_b=Eb, lifting_size=Z, Ncb=N, Nref=0,
+        nof_segment_bits=S, nof_filler_bits=F, rm_length=Ea,
+        tb_crc=tuple((crc >> s) & 0xff for s in ((16, 8, 0) if L == 24 else (8, 0))), cb_mode=False)
+    total = sum(w.size for w in want)
+    block = np.full(total, 0xEE, np.uint8)
+    packed = np.full(sum((w.size + 7) // 8 for w in want), 0xEE, np.uint8)
+    c = _lib.Context(0, launch_flags=_lib.LAUNCH_NO_DWQ if route == "launch" else 0)
+    try:
+        enc = hal.hw_accelerator_pdsch_enc_hip(c, cb_mode=False)
+        try:
+            enc.reserve_queue()
+            enc.configure_operation(cfg, 0)
+            assert enc.enqueue_operation(tb, None, 0)
+            while not enc.dequeue_operation(block, packed, 0):
+                pass
+            enc.free_queue()
+        finally:
+            enc.close()
+    finally:
+        c.close()
+    o = 0
+    for r, w in enumerate(want):
+        assert np.array_equal(block[o:o + w.size], w), f"segment {r} of {C} ({segs[r]} of {S} bits, starts at bit " \
+                                                       f"{(r * S) % 8} of its byte) differs from the oracle"
+        o += w.size
+    np.testing.assert_array_equal(packed, np.concatenate([np.packbits(w) for w in want]))

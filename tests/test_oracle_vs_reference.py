@@ -90,8 +90,19 @@ def test_encoder_all_graphs():
 
 
 def test_rate_matcher():
-    cases = C.rate_match_cases()
+    """rate_match_cases(), then the branch grid, every lifted graph and the staging rows of tests/rm_grid.py (all but
+    the 'division' rows, whose E the reference does not take)."""
+    cases = C.live_rate_match_cases()
+    assert sum("row" in c for c in cases) == 342 + 66 - 4
     _check("rate match", cases, [C.rate_match_input(c) for c in cases], C.run_rate_match)
+
+
+def test_encoder_on_the_rate_match_grid_messages():
+    """The codewords the grid's rows are cut from: the oracle encoder against the reference's on every grid message."""
+    from tests.rm_grid import all_rows
+    rows = all_rows()
+    cases = [dict(bg=c["bg"], Z=c["Z"], F=c["F"], L=O.BG_N_SHORT[c["bg"]] * c["Z"], seed=c["seed"]) for c in rows]
+    _check("encode (rate match grid)", cases, [C.rm_message(c) for c in rows], C.run_encode)
 
 
 def test_crc():
