@@ -621,6 +621,99 @@ int ldpc_hip_dmrs_pdsch_map_launch(ldpc_hip_ctx* ctx, uint32_t nof_descs, const 
                                    const float* weights, uint32_t nof_weights, const uint64_t* rb_masks,
                                    uint32_t nof_mask_words, void* d_grid, int output_format, void* stream);
 
+/* ---- PUSCH DM-RS: channel estimation from the received resource grid --------------------------------------------
+ * dmrs_pusch_estimator_impl::estimate (lib/phy/upper/signal_processors/dmrs_pusch_estimator_impl.cpp:71-212) over
+ * port_channel_estimator_average_impl::compute (port_channel_estimator_average_impl.cpp:215-408, 467-582, 608-720) and
+ * interpolator_linear_impl::interpolate (interpolator_linear_impl.cpp:32-79), per (rx port p, layer i) plane of a
+ * transmission: the pilots of the PDSCH DM-RS rule above with amplitude (float)M_SQRT1_2 and reference point 0, pilot j
+ * of RB n on subcarrier 12 n + 2 j + i / 2, the odd pilots of an odd layer negated; the LS sum over the DM-RS symbols
+ * in ascending order times 1.0F / ((float)nof_dmrs_symbols scaling); frequency-domain smoothing none or filter (the
+ * raised-cosine taps resampled at stride 2: 5 taps for 1 RB, 11 for 2, 15 for more, over min(12, taps / 2) virtual
+ * pilots per side, 6 for 1 RB); the linear interpolation as one float32 recurrence; cbf16 round-to-nearest-even to every
+ * symbol of [first_symbol, first_symbol + nof_symbols) at the allocated RBs. Elementwise values are the reference's bit
+ * for bit (built without its SIMD loops); the sums behind EPRE, RSRP, noise variance, SNR and CFO are fixed-shape trees
+ * and differ from the reference's sequential sums by the order alone; with the filter, hypotf, atan2f and sincosf of at
+ * most 24 virtual pilots per plane are the device's. DM-RS type 1, 1 to 4 layers (DM-RS ports 0 to 3) on 1 to 4 receive
+ * ports, 1 to 4 DM-RS symbols, no hopping, no CFO compensation (the CFO is estimated and reported), no time-alignment
+ * estimate. */
+#define LDPC_HIP_CHEST_NONE 0    /* port_channel_estimator_fd_smoothing_strategy::none   */
+#define LDPC_HIP_CHEST_FILTER 1  /* ::filter, what dmrs_pusch_estimator_factory_sw creates */
+/* Host only: 1 for type 1, 1 to 4 layers on 1 to 4 ports, strategy none or filter, compensate_cfo 0; else 0. */
+int ldpc_hip_dmrs_pusch_supported(uint32_t type, uint32_t nof_layers, uint32_t nof_rx_ports, uint32_t strategy,
+                                  uint32_t compensate_cfo);
+/* One transmission (dmrs_pusch_estimator::configuration). RB n is allocated when bit n % 64 of word mask_offset +
+ * n / 64 of `rb_masks` is set. Receive port p reads grid port rx_ports[p]: element grid_offset + rx_ports[p]
+ * grid_port_stride + l grid_symbol_stride + k of d_grid. Plane (layer i, port p) is plane i nof_rx_ports + p (the
+ * equalizer's order): its estimate of symbol l, subcarrier k is element est_offset + (i nof_rx_ports + p) plane_stride
+ * + l symbol_stride + k of d_estimates; its 6 A filtered pilots (A allocated RBs) are the cf32 elements pilots_offset +
+ * (i nof_rx_ports + p) 6 A .. of d_filtered_pilots, its sums record result_offset + i nof_rx_ports + p of d_results. */
+typedef struct {                 /* 104 bytes */
+  uint64_t grid_offset;          /* port 0, symbol 0, subcarrier 0 of the received grid, in elements from d_grid      */
+  uint64_t grid_symbol_stride;   /* elements between OFDM symbols of the grid, >= width                               */
+  uint64_t grid_port_stride;     /* elements between grid ports, >= (last DM-RS symbol) grid_symbol_stride + width    */
+  uint64_t est_offset;           /* plane 0, symbol 0, subcarrier 0 of the estimates, in elements from d_estimates    */
+  uint64_t symbol_stride;        /* elements between OFDM symbols of a plane, >= width                                */
+  uint64_t plane_stride;         /* elements between planes, >= (first_symbol + nof_symbols - 1) symbol_stride + width */
+  uint64_t pilots_offset;        /* the first plane's filtered pilots, in cf32 elements from d_filtered_pilots        */
+  uint32_t result_offset;        /* the first plane's record in d_results                                             */
+  uint32_t mask_offset;          /* the RB mask's first word in rb_masks; ceil(nof_rb / 64) words, none past nof_rb   */
+  uint32_t nof_rb;               /* resource blocks of the RB mask, <= 275                                            */
+  uint32_t width;                /* subcarriers of a row of the grid and of the estimates, >= 12 nof_rb               */
+  uint32_t grid_ports;           /* ports of the received grid; every rx_ports[p] is below it                         */
+  uint32_t slot_index;           /* slot_point::slot_index()                                                          */
+  uint32_t scrambling_id;        /* <= 65535                                                                          */
+  float    scaling;              /* > 0 and finite                                                                    */
+  uint16_t symbols_mask;         /* bit l: OFDM symbol l carries DM-RS; 1 to 4 bits, all inside the symbol range      */
+  uint8_t  type;                 /* 1                                                                                 */
+  uint8_t  nof_layers, nof_rx_ports;
+  uint8_t  n_scid;               /* 0 or 1                                                                            */
+  uint8_t  first_symbol, nof_symbols; /* nof_symbols >= 1, first_symbol + nof_symbols <= 14                           */
+  uint8_t  strategy;             /* LDPC_HIP_CHEST_NONE or LDPC_HIP_CHEST_FILTER                                      */
+  uint8_t  compensate_cfo;       /* 0                                                                                 */
+  uint8_t  rx_ports[4];
+  uint8_t  pad[2];
+} ldpc_hip_dmrs_pusch_desc;
+/* The raw sums of one plane: epre_sum = sum over the DM-RS symbols s of (E_s / n) n with E_s = sum |rx_s|^2 and
+ * n = nof_pilots; filt_power = sum |filtered|^2; noise_sum = sum over s of (N_s / n) n with N_s = sum |(filtered
+ * (-scaling + 0j)) x_s + rx_s|^2; (dot_re, dot_im) = sum prod_1 conj(prod_0) over the first two DM-RS symbols (0 with
+ * one); nof_pilots = 6 A, the pilots of one DM-RS symbol. */
+typedef struct {                 /* 32 bytes */
+  float    epre_sum, filt_power, noise_sum, dot_re, dot_im;
+  uint32_t nof_pilots;
+  uint32_t pad[2];
+} ldpc_hip_chest_result;
+/* What port_channel_estimator_average_impl.cpp:257-281 makes of them. */
+typedef struct {                 /* 24 bytes */
+  float   epre, rsrp, noise_var, snr, cfo_Hz;
+  int32_t has_cfo;               /* 0 with one DM-RS symbol (std::nullopt): cfo_Hz is then 0                          */
+} ldpc_hip_chest_metrics;
+/* Estimates nof_descs transmissions from a received device grid (cbf16) in one launch, asynchronously on `stream`
+ * (NULL = the context stream). descs and rb_masks (nof_mask_words words) are host arrays; they are uploaded into a
+ * per-context table of this launch's own (so that the launch may sit in one captured graph beside the equalizer's),
+ * which an equal call on the same stream reuses (so: launch once, then capture). output_format LDPC_HIP_SYM_CBF16:
+ * d_estimates holds cbf16 elements (4 bytes, aligned to 4); LDPC_HIP_SYM_CF32: cf32 elements (8 bytes, aligned to 8) of
+ * the same geometry, the values before the bf16 rounding. d_filtered_pilots (cf32) may be NULL; d_results takes one
+ * ldpc_hip_chest_result per plane. No byte outside a transmission's allocated RBs on the symbols of its range on its
+ * nof_layers x nof_rx_ports planes, its pilots and its records is written; a transmission with an empty RB mask is
+ * skipped. Transmissions whose outputs overlap are the caller's error and are not detected. LDPC_HIP_EINVAL (nothing is
+ * launched): a type other than 1, layers or ports outside 1 to 4, a strategy that is neither, compensate_cfo set, a
+ * scaling that is not > 0 or not finite, an empty symbols_mask, one with more than 4 bits or a bit outside
+ * [first_symbol, first_symbol + nof_symbols), nof_symbols of 0 or a range past symbol 14, nof_rb above 275, 12 nof_rb
+ * above width, width above a symbol stride, a DM-RS symbol's row past grid_port_stride or the range's last row past
+ * plane_stride, an offset or stride of 2^48 elements or more, an RB mask outside its array or a mask bit at or past
+ * nof_rb, scrambling_id above 65535, n_scid above 1, an rx_ports entry at or above grid_ports, an output_format that is
+ * neither, a null required argument. */
+int ldpc_hip_dmrs_pusch_estimate_launch(ldpc_hip_ctx* ctx, uint32_t nof_descs, const ldpc_hip_dmrs_pusch_desc* descs,
+                                        const uint64_t* rb_masks, uint32_t nof_mask_words, const void* d_grid,
+                                        void* d_estimates, int output_format, void* d_filtered_pilots /* may be NULL */,
+                                        void* d_results, void* stream);
+/* Host only: epre, rsrp, noise variance (floored at rsrp / 10^10), snr and cfo_Hz of one plane from its raw sums, in
+ * float32 in the reference's order with the host's libm. l0 and l1 are the first two DM-RS symbols (l1 ignored with
+ * nof_dmrs_symbols 1), scs the numerology 0 to 4 (15 kHz 2^scs). LDPC_HIP_EINVAL: a null argument, nof_dmrs_symbols
+ * outside 1 to 4, a symbol at or above 14, l1 <= l0, scs above 4, scaling not > 0, no pilots. */
+int ldpc_hip_dmrs_pusch_finalize(const ldpc_hip_chest_result* sums, float scaling, uint32_t nof_dmrs_symbols,
+                                 uint32_t l0, uint32_t l1, uint32_t scs, ldpc_hip_chest_metrics* out);
+
 /* ---- launch graphs: one submission per slot ---------------------------------------------------------------- */
 /* srsRAN runs the PUSCH decode chain once per slot with the same shape slot after slot (pusch_decoder_impl /
  * pusch_decoder_hw_impl call the decoder per codeblock and join per TB). Here the chain's *_launch calls on `stream`

@@ -45,7 +45,9 @@ EXPORTED_SYMBOLS = [
     "ldpc_hip_equalize_supported", "ldpc_hip_equalize_launch", "ldpc_hip_equalize_sync",
     "ldpc_hip_precode_supported", "ldpc_hip_precode_map_launch", "ldpc_hip_precode_sync",
     "ldpc_hip_dmrs_pdsch_supported", "ldpc_hip_dmrs_pdsch_c_init", "ldpc_hip_dmrs_pdsch_map_launch",
+    "ldpc_hip_dmrs_pusch_supported", "ldpc_hip_dmrs_pusch_estimate_launch", "ldpc_hip_dmrs_pusch_finalize",
 ]
+CHEST_NONE, CHEST_FILTER = 0, 1   # LDPC_HIP_CHEST_*
 SYM_CF32, SYM_CI8, SYM_CBF16 = 0, 1, 2   # LDPC_HIP_SYM_*
 EQ_ZF, EQ_MMSE = 0, 1      # LDPC_HIP_EQ_*
 HARQ_STRIDE = 25344   # LDPC_HIP_HARQ_STRIDE
@@ -200,6 +202,36 @@ class DmrsPdschDesc(ctypes.Structure):
 assert ctypes.sizeof(DmrsPdschDesc) == 64
 
 
+class DmrsPuschDesc(ctypes.Structure):
+    """ldpc_hip_dmrs_pusch_desc (include/srsran_ldpc_hip.h)."""
+    _fields_ = [("grid_offset", ctypes.c_uint64), ("grid_symbol_stride", ctypes.c_uint64),
+                ("grid_port_stride", ctypes.c_uint64), ("est_offset", ctypes.c_uint64),
+                ("symbol_stride", ctypes.c_uint64), ("plane_stride", ctypes.c_uint64),
+                ("pilots_offset", ctypes.c_uint64), ("result_offset", ctypes.c_uint32),
+                ("mask_offset", ctypes.c_uint32), ("nof_rb", ctypes.c_uint32), ("width", ctypes.c_uint32),
+                ("grid_ports", ctypes.c_uint32), ("slot_index", ctypes.c_uint32), ("scrambling_id", ctypes.c_uint32),
+                ("scaling", ctypes.c_float), ("symbols_mask", ctypes.c_uint16), ("type", ctypes.c_uint8),
+                ("nof_layers", ctypes.c_uint8), ("nof_rx_ports", ctypes.c_uint8), ("n_scid", ctypes.c_uint8),
+                ("first_symbol", ctypes.c_uint8), ("nof_symbols", ctypes.c_uint8), ("strategy", ctypes.c_uint8),
+                ("compensate_cfo", ctypes.c_uint8), ("rx_ports", ctypes.c_uint8 * 4), ("pad", ctypes.c_uint8 * 2)]
+
+
+class ChestResult(ctypes.Structure):
+    """ldpc_hip_chest_result (include/srsran_ldpc_hip.h)."""
+    _fields_ = [("epre_sum", ctypes.c_float), ("filt_power", ctypes.c_float), ("noise_sum", ctypes.c_float),
+                ("dot_re", ctypes.c_float), ("dot_im", ctypes.c_float), ("nof_pilots", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32 * 2)]
+
+
+class ChestMetrics(ctypes.Structure):
+    """ldpc_hip_chest_metrics (include/srsran_ldpc_hip.h)."""
+    _fields_ = [("epre", ctypes.c_float), ("rsrp", ctypes.c_float), ("noise_var", ctypes.c_float),
+                ("snr", ctypes.c_float), ("cfo_Hz", ctypes.c_float), ("has_cfo", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(DmrsPuschDesc) == 104 and ctypes.sizeof(ChestResult) == 32 and ctypes.sizeof(ChestMetrics) == 24
+
+
 class TbResult(ctypes.Structure):
     _fields_ = [("tb_crc_ok", ctypes.c_uint8), ("written", ctypes.c_uint8), ("nof_cbs_ok", ctypes.c_uint16)]
 
@@ -289,6 +321,10 @@ def load():
         "ldpc_hip_dmrs_pdsch_supported": (I, [U32, U32, U32]),
         "ldpc_hip_dmrs_pdsch_c_init": (U32, [U32, U32, U32, U32]),
         "ldpc_hip_dmrs_pdsch_map_launch": (I, [P, U32, ctypes.POINTER(DmrsPdschDesc), P, U32, P, U32, P, I, P]),
+        "ldpc_hip_dmrs_pusch_supported": (I, [U32, U32, U32, U32, U32]),
+        "ldpc_hip_dmrs_pusch_estimate_launch": (I, [P, U32, ctypes.POINTER(DmrsPuschDesc), P, U32, P, P, I, P, P, P]),
+        "ldpc_hip_dmrs_pusch_finalize": (I, [ctypes.POINTER(ChestResult), ctypes.c_float, U32, U32, U32, U32,
+                                             ctypes.POINTER(ChestMetrics)]),
         "ldpc_hip_capture_begin": (I, [P, P]),
         "ldpc_hip_capture_end": (I, [P, P, ctypes.POINTER(P)]),
         "ldpc_hip_graph_launch": (I, [P, P]),

@@ -3,10 +3,11 @@
  * queue's operations and the external HARQ repository, with the functions its units call across each other:
  * ldpc_hip_api.cpp (context, plans, *_launch entry points), ldpc_hip_sync.cpp (synchronous entry points),
  * ldpc_hip_modulate.cpp (modulation mapper), ldpc_hip_equalize.cpp (channel equalizer), ldpc_hip_precode.cpp
- * (precoder), ldpc_hip_dmrs.cpp (PDSCH DM-RS), ldpc_hip_hal.cpp (HAL decoder queue), ldpc_hip_enc_queue.cpp (PDSCH
- * encoder queue) and ldpc_hip_descs.cpp (descriptor translations, the precoder's and the DM-RS generator's tables among
- * them, host only). The segment stages share the two tails here: launch_items (work items up, one launch) and
- * sync_round_trip (a *_sync call's host buffers through the scratch).
+ * (precoder), ldpc_hip_dmrs.cpp (PDSCH DM-RS), ldpc_hip_chest.cpp (PUSCH DM-RS channel estimator), ldpc_hip_hal.cpp
+ * (HAL decoder queue), ldpc_hip_enc_queue.cpp (PDSCH encoder queue) and ldpc_hip_descs.cpp (descriptor translations,
+ * the precoder's, the DM-RS generator's and the channel estimator's tables among them, host only). The segment stages
+ * share the two tails here: launch_items (work items up, one launch) and sync_round_trip (a *_sync call's host buffers
+ * through the scratch).
  */
 #pragma once
 
@@ -199,6 +200,7 @@ struct ldpc_hip_ctx {
   ldpc_hip::desc_table    d_eqsegs;  /* ldpc_hip_equalize_launch segments */
   ldpc_hip::desc_table    d_precode; /* ldpc_hip_precode_map_launch / _sync: make_precode_table's blob, as bytes */
   ldpc_hip::desc_table    d_dmrs;    /* ldpc_hip_dmrs_pdsch_map_launch: make_dmrs_table's blob, as bytes */
+  ldpc_hip::desc_table    d_chest;   /* ldpc_hip_dmrs_pusch_estimate_launch: make_chest_table's blob, as bytes */
   ldpc_hip::desc_table    d_tbaux;   /* ldpc_hip_tb_join_launch: its TB's descriptor, TB and chunk per workgroup */
   ldpc_hip::dev_buffer    d_tbwork;  /* ldpc_hip_tb_join_launch: per-TB chunk CRCs + arrival counter (zero at rest) */
   ldpc_hip::demod_tables  dtab{};    /* demodulator slopes / intercepts (make_demod_tables) */

@@ -20,6 +20,9 @@ static_assert(sizeof(ldpc_hip_enc_desc) == 24, "ldpc_hip_enc_desc layout");
 static_assert(sizeof(ldpc_hip_rm_desc) == 32, "ldpc_hip_rm_desc layout");
 static_assert(sizeof(ldpc_hip_demod_desc) == 32, "ldpc_hip_demod_desc layout");
 static_assert(sizeof(ldpc_hip_dmrs_pdsch_desc) == 64, "ldpc_hip_dmrs_pdsch_desc layout");
+static_assert(sizeof(ldpc_hip_dmrs_pusch_desc) == 104, "ldpc_hip_dmrs_pusch_desc layout");
+static_assert(sizeof(ldpc_hip_chest_result) == sizeof(chest_record), "ldpc_hip_chest_result layout");
+static_assert(sizeof(ldpc_hip_chest_metrics) == 24, "ldpc_hip_chest_metrics layout");
 
 namespace {
 
@@ -666,6 +669,254 @@ const char* make_dmrs_table(uint32_t n, const ldpc_hip_dmrs_pdsch_desc* descs, c
   std::memcpy(t.blob.data(), t.rows.data(), t.words_at);
   std::memcpy(t.blob.data() + t.words_at, words.data(), t.weights_at - t.words_at);
   std::memcpy(t.blob.data() + t.weights_at, weights, 8U * static_cast<size_t>(nof_weights));
+  return nullptr;
+}
+
+/* ---- PUSCH DM-RS channel estimator ---- */
+namespace {
+/* RC_FILTER (port_channel_estimator_average_impl.cpp:42-47): raised cosine, roll-off 0.2, 3 symbols, 10 samples each */
+constexpr float CHEST_RC[31] = {-0.0641253F, -0.0660711F, -0.0611526F, -0.0485918F, -0.0281126F, 0.0000000F,  0.0348830F,
+                                0.0751249F,  0.1188406F,  0.1637874F,  0.2075139F,  0.2475302F,  0.2814857F,  0.3073415F,
+                                0.3235207F,  0.3290274F,  0.3235207F,  0.3073415F,  0.2814857F,  0.2475302F,  0.2075139F,
+                                0.1637874F,  0.1188406F,  0.0751249F,  0.0348830F,  0.0000000F,  -0.0281126F, -0.0485918F,
+                                -0.0611526F, -0.0660711F, -0.0641253F};
+} // namespace
+
+uint32_t chest_filter(uint32_t nof_rb, float* taps)
+{
+  const uint32_t stride = 2;
+  nof_rb                = std::min(nof_rb, 3U);
+  const uint32_t half   = (nof_rb * 10U + 1U) / 2U / stride;
+  const uint32_t ntaps  = 2U * half + 1U;
+  uint32_t       n      = 31U / 2U - half * stride;
+  float          total  = 0;
+  for (uint32_t i = 0; i != ntaps; ++i, n += stride) {
+    taps[i] = CHEST_RC[n];
+    total += taps[i];
+  }
+  const float h = 1 / total;
+  for (uint32_t i = 0; i != CHEST_MAX_TAPS; ++i) {
+    taps[i] = i < ntaps ? taps[i] * h : 0.0F;
+  }
+  return ntaps;
+}
+
+uint32_t chest_virtual_pilots(uint32_t nof_rb)
+{
+  float taps[CHEST_MAX_TAPS];
+  return nof_rb == 1 ? CHEST_DPR : std::min(CHEST_MAX_VPILOTS, chest_filter(nof_rb, taps) / 2U);
+}
+
+const char* make_chest_table(uint32_t n, const ldpc_hip_dmrs_pusch_desc* descs, const uint64_t* rb_masks,
+                             uint32_t nof_mask_words, chest_table& t)
+{
+  t = chest_table{};
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> seen;
+  std::vector<uint64_t>                             words;
+  for (uint32_t i = 0; i != n; ++i) {
+    const ldpc_hip_dmrs_pusch_desc& d = descs[i];
+    if (d.type != 1) {
+      return "dmrs_pusch: only DM-RS type 1";
+    }
+    if (d.nof_layers < 1 || d.nof_layers > CHEST_MAX_LAYERS || d.nof_rx_ports < 1 ||
+        d.nof_rx_ports > CHEST_MAX_PORTS) {
+      return "dmrs_pusch: unsupported topology (1 to 4 layers on 1 to 4 receive ports)";
+    }
+    if (d.strategy != LDPC_HIP_CHEST_NONE && d.strategy != LDPC_HIP_CHEST_FILTER) {
+      return "dmrs_pusch: the smoothing strategy is LDPC_HIP_CHEST_NONE or LDPC_HIP_CHEST_FILTER";
+    }
+    if (d.compensate_cfo != 0) {
+      return "dmrs_pusch: CFO compensation is not supported";
+    }
+    if (!(d.scaling > 0.0F) || !std::isfinite(d.scaling)) {
+      return "dmrs_pusch: the scaling is not positive or not finite";
+    }
+    if (d.scrambling_id > 65535U) {
+      return "dmrs_pusch: scrambling_id above 65535";
+    }
+    if (d.n_scid > 1U) {
+      return "dmrs_pusch: n_scid above 1";
+    }
+    if (d.nof_symbols == 0 || static_cast<uint32_t>(d.first_symbol) + d.nof_symbols > CHEST_NSYMB) {
+      return "dmrs_pusch: the symbol range is empty or passes symbol 14";
+    }
+    if (d.symbols_mask == 0) {
+      return "dmrs_pusch: an empty symbol mask";
+    }
+    const uint32_t range = ((1U << d.nof_symbols) - 1U) << d.first_symbol;
+    if ((d.symbols_mask & ~range) != 0) {
+      return "dmrs_pusch: a DM-RS symbol outside the symbol range";
+    }
+    const uint32_t nsym = static_cast<uint32_t>(__builtin_popcount(d.symbols_mask));
+    if (nsym > CHEST_MAX_DMRS) {
+      return "dmrs_pusch: more than 4 DM-RS symbols";
+    }
+    if (d.nof_rb > CHEST_MAX_RB) {
+      return "dmrs_pusch: nof_rb above 275";
+    }
+    if (12ULL * d.nof_rb > d.width) {
+      return "dmrs_pusch: 12 nof_rb above the row's width";
+    }
+    if (d.width > d.grid_symbol_stride || d.width > d.symbol_stride) {
+      return "dmrs_pusch: a row is wider than a symbol stride";
+    }
+    /* no base, plane or row can then wrap 64 bits: at most 16 planes, 4 ports, 14 symbols and 6 x 275 pilots a plane */
+    for (uint64_t v : {d.grid_offset, d.grid_symbol_stride, d.grid_port_stride, d.est_offset, d.symbol_stride,
+                       d.plane_stride, d.pilots_offset}) {
+      if (v >= (1ULL << 48)) {
+        return "dmrs_pusch: an offset or stride of 2^48 elements or more";
+      }
+    }
+    const uint32_t l_dmrs = 31U - static_cast<uint32_t>(__builtin_clz(d.symbols_mask));
+    if (d.grid_symbol_stride > (~0ULL - d.width) / CHEST_NSYMB ||
+        l_dmrs * d.grid_symbol_stride + d.width > d.grid_port_stride) {
+      return "dmrs_pusch: the DM-RS symbols are wider than the grid's port stride";
+    }
+    const uint32_t l_last = static_cast<uint32_t>(d.first_symbol) + d.nof_symbols - 1U;
+    if (d.symbol_stride > (~0ULL - d.width) / CHEST_NSYMB || l_last * d.symbol_stride + d.width > d.plane_stride) {
+      return "dmrs_pusch: the symbol range is wider than the plane stride";
+    }
+    for (uint32_t p = 0; p != d.nof_rx_ports; ++p) {
+      if (d.rx_ports[p] >= d.grid_ports) {
+        return "dmrs_pusch: an rx port at or above the grid's ports";
+      }
+    }
+    const uint32_t nw = (d.nof_rb + 63U) / 64U;
+    if (d.mask_offset > nof_mask_words || nw > nof_mask_words - d.mask_offset) {
+      return "dmrs_pusch: an RB mask lies outside the masks";
+    }
+    const uint64_t* m = rb_masks + d.mask_offset;
+    if (d.nof_rb % 64U != 0 && (m[nw - 1] >> (d.nof_rb % 64U)) != 0) {
+      return "dmrs_pusch: an RB-mask bit beyond nof_rb";
+    }
+    uint32_t lo = nw, hi = 0, count = 0;
+    for (uint32_t w = 0; w != nw; ++w) {
+      if (m[w] != 0) {
+        lo = lo == nw ? w : lo;
+        hi = w;
+        count += static_cast<uint32_t>(__builtin_popcountll(m[w]));
+      }
+    }
+    if (lo == nw) {
+      continue; /* no allocated RB */
+    }
+    auto it = seen.find({d.mask_offset, nw});
+    if (it == seen.end()) {
+      it = seen.emplace(std::make_pair(d.mask_offset, nw), static_cast<uint32_t>(words.size())).first;
+      words.insert(words.end(), m, m + nw);
+    }
+    chest_plane r{};
+    r.grid_sym_stride = d.grid_symbol_stride;
+    r.est_sym_stride  = d.symbol_stride;
+    r.word0           = it->second;
+    r.rb_begin        = lo * 64U + static_cast<uint32_t>(__builtin_ctzll(m[lo]));
+    r.rb_end          = hi * 64U + 64U - static_cast<uint32_t>(__builtin_clzll(m[hi]));
+    r.n_rb            = count;
+    r.nsym            = static_cast<uint8_t>(nsym);
+    for (uint32_t l = 0, s = 0; l != CHEST_NSYMB; ++l) {
+      if (((d.symbols_mask >> l) & 1U) != 0) {
+        /* the sequence of the symbol from its first used bit: RB rb_begin's pilot 0 */
+        const ldpc_hip_prs_state st =
+            prs_state_at(dmrs_c_init(d.slot_index, l, d.scrambling_id, d.n_scid), 2ULL * CHEST_DPR * r.rb_begin);
+        r.x1[s]       = st.x1;
+        r.x2[s]       = st.x2;
+        r.dmrs_sym[s] = static_cast<uint8_t>(l);
+        ++s;
+      }
+    }
+    /* port_channel_estimator_average_impl.cpp:334-335 */
+    r.total_scaling = 1.0F / (static_cast<float>(nsym) * d.scaling);
+    r.beta          = d.scaling;
+    r.first_symbol  = d.first_symbol;
+    r.nof_symbols   = d.nof_symbols;
+    r.filter        = CHEST_NO_FILTER;
+    if (d.strategy == LDPC_HIP_CHEST_FILTER) {
+      float taps[CHEST_MAX_TAPS];
+      r.filter = static_cast<uint8_t>(std::min(count, CHEST_NOF_FILTERS) - 1U);
+      r.ntaps  = static_cast<uint8_t>(chest_filter(count, taps));
+      r.nvp    = static_cast<uint8_t>(chest_virtual_pilots(count));
+    }
+    r.wide = d.symbol_stride % 4U == 0 ? 1 : 0;
+    for (uint32_t layer = 0; layer != d.nof_layers; ++layer) {
+      for (uint32_t p = 0; p != d.nof_rx_ports; ++p) {
+        const uint64_t plane = static_cast<uint64_t>(layer) * d.nof_rx_ports + p;
+        chest_plane    q     = r;
+        q.grid_base          = d.grid_offset + d.rx_ports[p] * d.grid_port_stride;
+        q.est_base           = d.est_offset + plane * d.plane_stride;
+        q.pil_base           = d.pilots_offset + plane * CHEST_DPR * count;
+        q.res_index          = d.result_offset + static_cast<uint32_t>(plane);
+        q.layer              = static_cast<uint8_t>(layer);
+        q.wide               = r.wide != 0 && q.est_base % 4U == 0 ? 1 : 0;
+        q.block0             = static_cast<uint32_t>(t.planes.size());
+        if (t.planes.size() >= MAX_LAUNCH_BLOCKS) {
+          return "dmrs_pusch: too many planes in one launch";
+        }
+        t.planes.push_back(q);
+      }
+    }
+  }
+  if (t.planes.empty()) {
+    return nullptr; /* nothing to launch: an empty blob */
+  }
+  t.words_at   = t.planes.size() * sizeof(chest_plane);
+  t.filters_at = t.words_at + words.size() * sizeof(uint64_t);
+  float filters[CHEST_NOF_FILTERS][CHEST_TAP_STRIDE] = {};
+  for (uint32_t f = 0; f != CHEST_NOF_FILTERS; ++f) {
+    chest_filter(f + 1U, filters[f]);
+  }
+  t.blob.resize(t.filters_at + sizeof(filters));
+  std::memcpy(t.blob.data(), t.planes.data(), t.words_at);
+  std::memcpy(t.blob.data() + t.words_at, words.data(), t.filters_at - t.words_at);
+  std::memcpy(t.blob.data() + t.filters_at, filters, sizeof(filters));
+  return nullptr;
+}
+
+const char* chest_finalize(const ldpc_hip_chest_result& r, float scaling, uint32_t nsym, uint32_t l0, uint32_t l1,
+                           uint32_t scs, ldpc_hip_chest_metrics& out)
+{
+  if (nsym < 1 || nsym > CHEST_MAX_DMRS || l0 >= CHEST_NSYMB || scs > 4 || !(scaling > 0.0F) || r.nof_pilots == 0) {
+    return "dmrs_pusch_finalize: an argument outside its range";
+  }
+  if (nsym > 1 && (l1 >= CHEST_NSYMB || l1 <= l0)) {
+    return "dmrs_pusch_finalize: the second DM-RS symbol is not after the first inside the slot";
+  }
+  out = ldpc_hip_chest_metrics{};
+  const float    n      = static_cast<float>(r.nof_pilots);
+  const unsigned pilots = r.nof_pilots * nsym;
+  const unsigned khz    = 15U << scs;
+  /* :357, then :257-281 */
+  float rsrp = 0;
+  rsrp += r.filt_power / n * n * scaling * scaling * static_cast<float>(nsym);
+  float epre = 0;
+  epre += r.epre_sum;
+  float noise_var = 0;
+  noise_var += r.noise_sum;
+  rsrp /= static_cast<float>(pilots);
+  epre /= static_cast<float>(pilots);
+  noise_var /= static_cast<float>(pilots - 1U);
+  const float min_noise_variance = rsrp / std::pow(10.0F, 100.0F / 10.0F);
+  noise_var                      = std::max(min_noise_variance, noise_var);
+  const float datarp             = rsrp / scaling / scaling;
+  out.epre                       = epre;
+  out.rsrp                       = rsrp;
+  out.noise_var                  = noise_var;
+  out.snr                        = (noise_var != 0) ? datarp / noise_var : 1000;
+  if (nsym > 1) {
+    /* :454-465: the symbols' start epochs in units of the symbol time, accumulated in float32 */
+    const double t_c = 1.0 / static_cast<double>(480000LL * 4096LL);
+    float        epochs[CHEST_NSYMB];
+    for (uint32_t i = 0; i != CHEST_NSYMB; ++i) {
+      const unsigned cp_len = (144U >> scs) + ((i == 0 || i == 7U * (1U << scs)) ? 16U : 0U);
+      const double   sec    = static_cast<double>(static_cast<int64_t>(cp_len) * 64) * t_c;
+      epochs[i] =
+          i == 0 ? static_cast<float>(sec * khz * 1000) : static_cast<float>(epochs[i - 1] + sec * khz * 1000 + 1.0F);
+    }
+    const float twopi       = 2.0F * static_cast<float>(M_PI);
+    const float noisy_phase = std::atan2(r.dot_im, r.dot_re);
+    const float cfo         = noisy_phase / twopi / (epochs[l1] - epochs[l0]);
+    out.cfo_Hz              = cfo * khz * 1000;
+    out.has_cfo             = 1;
+  }
   return nullptr;
 }
 

@@ -1,15 +1,16 @@
 /*
  * The one translation of each C-ABI descriptor (include/srsran_ldpc_hip.h) into the work item the kernels read
- * (ldpc_hip_device.h, ldpc_equalize.h, ldpc_precode.h, ldpc_dmrs.h), with its validation, the segment launches' and the
- * precoder's and the DM-RS generator's tables included. Host only: no HIP runtime call, no context. Each make_* returns
- * the reason its descriptor is invalid, or nullptr after filling the work item; the entry points report the reason
- * through ldpc_hip_last_error with LDPC_HIP_EINVAL.
+ * (ldpc_hip_device.h, ldpc_equalize.h, ldpc_precode.h, ldpc_dmrs.h, ldpc_chest.h), with its validation, the segment
+ * launches' and the precoder's, the DM-RS generator's and the channel estimator's tables included. Host only: no HIP
+ * runtime call, no context. Each make_* returns the reason its descriptor is invalid, or nullptr after filling the work
+ * item; the entry points report the reason through ldpc_hip_last_error with LDPC_HIP_EINVAL.
  */
 #pragma once
 
 #include <cstdint>
 #include <vector>
 
+#include "ldpc_chest.h"
 #include "ldpc_dmrs.h"
 #include "ldpc_equalize.h"
 #include "ldpc_graph.h"
@@ -135,5 +136,31 @@ struct dmrs_table {
  * RB, from block0. No row left: no blocks and an empty blob. */
 const char* make_dmrs_table(uint32_t n, const ldpc_hip_dmrs_pdsch_desc* descs, const float* weights,
                             uint32_t nof_weights, const uint64_t* rb_masks, uint32_t nof_mask_words, dmrs_table& t);
+
+/* ---- PUSCH DM-RS channel estimator ---- */
+/* The raised-cosine filter of port_channel_estimator_average_impl.cpp:74-101 for nof_rb RBs at stride 2: its taps
+ * (5, 11 or 15, normalised as the reference does, in float32) into taps[0 .. CHEST_MAX_TAPS); returns their number. */
+uint32_t chest_filter(uint32_t nof_rb, float* taps);
+/* the virtual pilots per side (port_channel_estimator_average_impl.cpp:629-632) */
+uint32_t chest_virtual_pilots(uint32_t nof_rb);
+/* a launch's table: planes, then RB-mask words, then the three filters, and the three as the launch uploads them:
+ * blob[0, words_at) the planes, [words_at, filters_at) the words (8 bytes each), then CHEST_NOF_FILTERS rows of
+ * CHEST_TAP_STRIDE floats */
+struct chest_table {
+  std::vector<chest_plane> planes;
+  std::vector<uint8_t>     blob;
+  size_t                   words_at = 0, filters_at = 0;
+};
+/* A launch's planes: every transmission in the caller's order (type, topology, strategy and compensate_cfo, scaling,
+ * scrambling_id and n_scid, the symbol range, the symbols mask inside it with 1 to 4 bits, nof_rb, 12 nof_rb against
+ * the width, the width against both symbol strides, the last DM-RS symbol's row against the grid's port stride and the
+ * range's last row against the plane stride, the rx ports against grid_ports, the RB mask's words inside `rb_masks`
+ * with no bit at or past nof_rb). A transmission with an empty RB mask is dropped; another becomes one plane per
+ * (layer, rx port), layer-major, its generator states at the first allocated RB. No plane left: an empty blob. */
+const char* make_chest_table(uint32_t n, const ldpc_hip_dmrs_pusch_desc* descs, const uint64_t* rb_masks,
+                             uint32_t nof_mask_words, chest_table& t);
+/* port_channel_estimator_average_impl.cpp:257-281, 454-465, 495-497 on a plane's raw sums; nullptr or the reason */
+const char* chest_finalize(const ldpc_hip_chest_result& r, float scaling, uint32_t nsym, uint32_t l0, uint32_t l1,
+                           uint32_t scs, ldpc_hip_chest_metrics& out);
 
 } // namespace ldpc_hip
